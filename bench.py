@@ -21,9 +21,14 @@ Launch:
     one rank per GPU; WORLD_SIZE must equal --gpus.
   --selftest: the same launch and argument path on CPU (gloo), exchanging a flat
     gradient buffer by the network's bucket plan (no GPU needed).
-Rank 0 prints ONE JSON line. At N = 1 it also carries sub-results measured in the
-same run for BASELINE configs[0] (CPU affine + the GPU GEMM of the same shape),
-configs[1] (forward only) and configs[4] (3072 model, MXFP8 GEMMs).
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the --steps steps
+and prints the headline with its roofline (the per-launch events of the timed steps).
+  --full: at N = 1 the line also carries what takes runs of its own: the HBM probe
+    (`box`), the sub-results for BASELINE configs[0] (CPU affine + the GPU GEMM of the
+    same shape), configs[1] (forward only) and configs[4] (3072 model, MXFP8 GEMMs), the
+    drop-in per-op path, the one-stream and every-row steps, and the CPU baseline.
+  --dump-outputs DIR: after the timed steps, what the last timed step computed
+    (DIR/<name>.npy, float32 / float64; see dump_outputs).
 """
 import argparse
 import json
@@ -57,6 +62,8 @@ MODEL_MFLOP_PER_FRAME = {"cnn_tdnn_17f.xconfig": (66.24, 198.68),
 # kf_prof classes (include/kf_ops.h) and the step classes the bench line reports
 PROF_CLASSES = {"gemm_fused": (0,), "conv_halo": (4,), "gemm_wgrad": (1,), "conv_wgrad": (5,),
                 "slab_reduce": (6,), "chain_num": (2,), "chain_den": (3,)}
+# --dump-outputs: values written per array (4 float32 arrays of 12 MiB: under 64 MB a dump)
+DUMP_MAX_VALUES = 3 << 20
 
 
 def parse(argv=None):
@@ -72,9 +79,14 @@ def parse(argv=None):
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--bucket-mb", type=float, default=16.0,
                    help="gradient all-reduce bucket size (N > 1)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the HBM probe, the N = 1 sub-results "
+                        "and the CPU baseline (default: the headline and its roofline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
     p.add_argument("--no-extra", action="store_true",
-                   help="skip the configs[0]/[1]/[4] sub-results at N = 1")
+                   help="with --full: skip the configs[0]/[1]/[4] sub-results at N = 1")
     p.add_argument("--extra-steps", type=int, default=5)
     p.add_argument("--cpu-frames", type=int, default=1500)
     p.add_argument("--gt-frames", type=int, default=48, help="frames of the gotorch-style float64 CPU leg")
@@ -186,6 +198,21 @@ def box_hbm_probe():
     torch.cuda.empty_cache()
     return {"copy_GBps": round(2 * 96000 * 1536 * 2 / (ms * 1e-3) / 1e9, 1),
             "probe": "torch copy of a [96000 x 1536] fp16 tensor (read + write), median of 10"}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy, float64 kept and everything else as
+    float32. An array of more than DUMP_MAX_VALUES values is written as a fixed sample of
+    its flattened values (the same seeded, sorted indices for a given size, so two builds
+    dump the same positions); smaller ones keep their shape."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        if arr.size > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(1234).integers(0, arr.size, DUMP_MAX_VALUES))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(arr, dtype=np.float64 if arr.dtype == np.float64 else np.float32))
 
 
 def host_cores():
@@ -454,8 +481,9 @@ def selftest(a, rank, world):
 
 
 # --------------------------------------------------------------------------- one workload
-def run_workload(a, xconfig, mode, fp8, rank, world, comm, steps, warmup, prof_on, keep=False):
+def run_workload(a, xconfig, mode, fp8, rank, world, comm, steps, warmup, prof_on, keep=False, dump=None):
     """Build the network, den graph and egs of one workload, time `steps` steps.
+    dump: directory for the last timed step's outputs (dump_outputs; rank 0).
     Returns (stats dict, context for the CPU baseline)."""
     import kfp16
     from kfp16 import chain, dp, synth
@@ -693,6 +721,17 @@ def run_workload(a, xconfig, mode, fp8, rank, world, comm, steps, warmup, prof_o
         stats = dp.sum_over_ranks([res.objf, res.num_logprob, res.den_logprob, res.frames, res.num_ok],
                                   "cpu")
         probe("dp.sum_over_ranks")
+    if dump and rank == 0:
+        # what a caller of the step holds after the last timed one: the output activation of
+        # its forward and, for the train step, the objective's statistics and output gradient,
+        # the flat weight gradient of its backward and the fp32 master weights after its SGD
+        arrays = {"output": net.read_activation("output")}
+        if mode == "train":
+            arrays["objective"] = np.asarray(stats, np.float64)   # objf, num / den logprob, frames, finite seqs
+            arrays["output_grad"] = gbuf.cpu().numpy()
+            arrays["grads"] = kfp16.read_f32(net.grad_ptr, (net.num_params,))
+            arrays["params"] = net.flat_params(net.get_params())
+        dump_outputs(dump, arrays)
     cpu_issue_ms = [(t_issue[i + 1] - t_issue[i]) * 1e3 for i in range(steps)]
     out = {"T": T, "elapsed": elapsed, "median_ms": median_ms, "step_ms": step_ms, "cpu_issue_ms": cpu_issue_ms, "steps": steps, "prof": prof, "chain_prof": chain_prof, "classes": classes,
            "xconfig": xconfig, "mode": mode, "h2d": h2d, "input_pool": npool, "rsub": rsub,
@@ -872,18 +911,20 @@ def main():
 
     prof_on = not a.no_prof
     peak = PEAK_FP8_TFLOPS if a.fp8 else PEAK_FP16_TFLOPS
-    box = box_hbm_probe()
+    # --full: everything beside the headline (the HBM probe, the sub-results, the CPU legs)
+    box = box_hbm_probe() if a.full else None
     head, ctx = run_workload(a, a.xconfig, a.mode, a.fp8, rank, world, comm, a.steps, a.warmup, prof_on,
-                             keep=True)
+                             keep=True, dump=a.dump_outputs)
     extra, errors = {}, {}
-    if world == 1 and not a.no_extra and a.xconfig == "cnn_tdnn_17f.xconfig" and a.mode == "train" and not a.fp8:
+    if (a.full and world == 1 and not a.no_extra and a.xconfig == "cnn_tdnn_17f.xconfig" and a.mode == "train"
+            and not a.fp8):
         extra, errors = sub_results(a, rank, world, prof_on)
 
     if rank == 0:
         # the box's CPU share (OMP_NUM_THREADS is set to it there; nproc shows the whole host)
         threads = a.cpu_threads or min(host_cores(), int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or
                                        host_cores())
-        if world == 1 and not a.no_extra and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_extra and not a.no_cpu_baseline:
             try:
                 extra["configs[0]_affine_40x512"] = config1_affine(threads)
             except Exception as e:  # noqa: BLE001 -- recorded; the headline still prints
@@ -898,7 +939,7 @@ def main():
         out = {
             "metric": METRIC_FWD if fwd_only else METRIC, "value": d["value"], "unit": "frames/sec",
             "n_gpus": world, "rccl_ranks": rccl_ranks,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": d["ms_per_step"],
+            "steps": a.steps, "warmup": a.warmup, "full": bool(a.full), "ms_per_step": d["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "mxfp8 GEMMs (e4m3 + E8M0), fp16 storage" if a.fp8 else "fp16",
             "data": "synthetic",
@@ -927,7 +968,8 @@ def main():
                   "objective_finite_seqs"):
             if k in d:
                 out[k] = d[k]
-        out["box"] = box
+        if box is not None:
+            out["box"] = box
         out["wgrad_stream"] = not a.no_wgrad_stream
         out["implicit_dz"] = bool(a.implicit_dz)
         if not fwd_only:
@@ -953,7 +995,7 @@ def main():
             rl["traffic"] = (pmc_traffic(rl["kernel"]) if (a.xconfig == "cnn_tdnn_17f.xconfig" and not a.fp8
                                                            and a.mode == "train") else None)
             out["roofline"] = rl
-        if world == 1 and not a.no_cpu_baseline and not fwd_only:
+        if a.full and world == 1 and not a.no_cpu_baseline and not fwd_only:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle
             from kfp16 import synth
