@@ -154,7 +154,7 @@ int nnet_row_set(const KfNet *net, int *tc, int *tc0);
 int nnet_set_implicit_dz(KfNet *net, int on);
 
 /* diagnostics (tests) of the two-stream backward: main_aff chooses where the TDNN-F
- * affine weight gradients run (-1 = KF_BWD_MAIN_AFF / the default 0: all on the
+ * affine weight gradients run (0, the default, and -1: all on the
  * weight-gradient stream; 1 = every other one on the input-gradient chain; 2 = all on the
  * chain);
  * stall_cycles > 0 queues a spin kernel of that many GPU clock cycles (kf_debug_spin) on

@@ -1,0 +1,990 @@
+// backward.cpp — the backward pass of the C++ host layer (Network.Backward,
+// network_backward.go:94-143): exact gradients of forward.cpp's launches. BackwardPass owns
+// the streams and the gradient ring; one member function per layer kind does the launches.
+#include <climits>
+#include <cstdlib>
+
+#include "net_internal.h"
+
+namespace {
+
+// ring index of an input-gradient buffer, or -1
+int dz_index(const KfNet *net, const void *p) {
+    for (int i = 0; i < 3; ++i)
+        if (p == net->dz[i]) return i;
+    return -1;
+}
+
+// Epilogue of an input-gradient GEMM that produces the gradient of layer P
+// (the input of the layer being back-propagated). v = acc (+ bypass * g_cur):
+//   g_P = rne(v) when P itself has a bypass (its own input gradient needs it)
+//   dz_P = rne(v * bnscale_P * mask_P) for relu+BN layers, rne(v*bn2scale) for prefinal
+bool dx_epilogue(KfNet *net, int P, void *dz_out, void *g_out, KfEpilogue &E) {
+    E = epi0();
+    NetLayer &pl = net->layers[P];
+    const Layer &L = pl.L;
+    const int w = L.out_dim;
+    E.ldo2 = w;
+    E.out2 = dz_out;
+    const int di = dz_index(net, dz_out);
+    if (di >= 0) net->dz_imp[di] = net->dz_edge[di] = false;
+    switch (L.type) {
+        case LayerType::TDNNF: {
+            E.scale2 = pl.bn_scale;
+            E.mask_in = pl.mask;
+            if (pl.bypass) {
+                E.out = g_out;
+                E.ldo = w;
+                // implicit dz: g is stored anyway, its consumers apply mask and scale (the
+                // masked weight gradient needs 256-column tiles: w > 128, not 160 / 320)
+                const bool shape_ok = w > 128 && !(w % 160 == 0 && w <= 320);
+                if (net->implicit_dz && !net->fp8 && di >= 0 && pl.mask && pl.bn_scale && net->w2s && shape_ok) {
+                    E.out2 = nullptr;
+                    E.scale2 = nullptr;
+                    E.mask_in = nullptr;
+                    net->dz_imp[di] = true;
+                    return true;
+                }
+            }
+            // a strided P's clamped-splice edge row (row T of dz: sum of its rows T-1-s .. T-1),
+            // summed by the epilogue's last row tile instead of a separate kf_rows_sum launch
+            if (L.time_stride > 0 && di >= 0 && net->T > 0 && !(net->rs.Tc && pl.compact)) {
+                const int T = net->T;
+                E.edge_out = (char *)dz_out + (size_t)T * w * 2;
+                E.edge_r0 = T - 1 - L.time_stride < 0 ? 0 : T - 1 - L.time_stride;
+                E.edge_r1 = T;
+                E.edge_src = 1;
+                net->dz_edge[di] = true;
+            }
+            // MXFP8 train step: also the e4m3 copy of dz_P for P's affine input gradient; only
+            // when the copy's row is exactly w wide (w % 128 == 0), so the dgrad GEMM's K range
+            // holds no stale codes from a wider layer's copy
+            if (net->fp8 && net->fp8_dgrad && di >= 0 && w % 128 == 0 && pl.w8d.q && net->dz8[di].q &&
+                net->dz8[di].ld == w) {
+                E.out8 = net->dz8[di].q;
+                E.ldo8 = net->dz8[di].ld;
+                E.scale8 = net->dz8[di].s;
+                E.out8_src = 1;
+                net->dz8_layer[di] = P;
+            }
+            return true;
+        }
+        case LayerType::ConvReluBN:
+        case LayerType::Attention:
+            E.scale2 = pl.bn_scale;
+            E.mask_in = pl.mask;
+            return true;
+        case LayerType::Prefinal:
+            if (pl.has_bn2) E.scale2 = pl.bn2_scale;
+            return true;
+        case LayerType::Batchnorm:
+            // batchnorm-component (frozen statistics): the gradient at its input is the
+            // output gradient times its per-column scale (backward_wrappers.cu:105-115),
+            // applied in the producing GEMM's epilogue; the step through the BN layer is
+            // then a pass-through (BackwardPass::step). Its own input must take a raw gradient.
+            if (pl.input < 0 || !(net->layers[pl.input].L.type == LayerType::Linear)) {
+                set_err("backward: gradient through batchnorm-component " + L.name +
+                        " into a layer other than linear-component is not supported");
+                return false;
+            }
+            E.scale2 = pl.bn_scale;
+            return true;
+        case LayerType::Linear:
+        case LayerType::CombineFeatureMaps:  // raw gradient; its backward splits it (ivector branch)
+            return true;
+        default:
+            set_err("backward: gradient into layer " + L.name + " is not supported");
+            return false;
+    }
+}
+
+// issue every bucket planned to follow backward step `step` (INT_MAX: all left)
+bool dp_issue(KfNet *net, size_t &next, int step) {
+    for (; next < net->dp_after.size() && net->dp_after[next] <= step; ++next)
+        if (kf_dp_allreduce_mean_async(net->dp, net->grad + net->dp_begin[next],
+                                       (size_t)(net->dp_end[next] - net->dp_begin[next])) != 0) {
+            const char *e = kf_dp_last_error();
+            set_err(std::string("dp all-reduce: ") + (e ? e : ""));
+            return false;
+        }
+    return true;
+}
+
+// conv input gradient with the weights as a plain [taps * fout x fin] B, N contiguous (the
+// forward's B layout): block i = (tap taps[i]'s fin rows of W)^T, one batched transpose per
+// layer and step. The shifted k-contiguous weight rows (op_wrows, the BROW halo kernels) ran
+// cnn4's input gradient at half the forward's rate. KF_DGRAD_WT=0: op_wrows. The K order is
+// the same either way, so the result is bit-identical.
+bool dgrad_wt_on() {
+    const char *e = getenv("KF_DGRAD_WT");
+    return !(e && e[0] == '0');
+}
+void *dgrad_wt(KfNet *net, NetLayer &nl, const std::vector<int> &taps) {
+    const Layer &L = nl.L;
+    const size_t blk = (size_t)L.fin * L.fout * 2;
+    if ((int)taps.size() > KF_TRANSPOSE_MAX || taps.size() > nl.dt.size()) return nullptr;
+    if (!nl.wtd) nl.wtd = net->dalloc(nl.dt.size() * blk);
+    if (!nl.wtd) return nullptr;
+    std::vector<const void *> src;
+    std::vector<void *> dst;
+    std::vector<int> M, N;
+    for (size_t i = 0; i < taps.size(); ++i) {
+        src.push_back((const char *)wptr(net, nl.pW) + taps[i] * blk);
+        dst.push_back((char *)nl.wtd + i * blk);
+        M.push_back(L.fin);
+        N.push_back(L.fout);
+    }
+    if (kf_transpose_batch((int)taps.size(), src.data(), dst.data(), M.data(), N.data()) != 0) return nullptr;
+    return nl.wtd;
+}
+
+// E at input frame f of a conv layer's input gradient viewed as [(t,h) x fin]
+KfEpilogue at_frame(const KfEpilogue &E, const Layer &L, long long f) {
+    const long long off = f * L.hin * L.fin;
+    KfEpilogue X = E;
+    X.ldo2 = L.fin;
+    X.out2 = (char *)E.out2 + off * 2;
+    if (E.out) {
+        X.ldo = L.fin;
+        X.out = (char *)E.out + off * 2;
+    }
+    if (E.mask_in) X.mask_in = E.mask_in + off / 8;
+    if (E.mask_out) X.mask_out = E.mask_out + off / 8;
+    return X;
+}
+
+// one layer's backward step
+struct Step {
+    NetLayer &nl;
+    int li;
+    int T, Tfull;       // the layer's rows (compact above the conv stack, row subsampling) / the forward's
+    const void *x;      // the layer's input, as its forward read it
+    bool want_dx;       // a trainable layer lies below
+    bool to_full;       // the first compact layer: its input gradient is scattered to full rows
+    void *dz_next, *g_next, *dbott_buf;
+    KfEpilogue E;       // of the GEMM that produces the input gradient (dx_epilogue)
+};
+// a TDNN-F step's shapes and buffers
+struct Tdnnf {
+    int s, bn, klin, kaff;
+    int ib;             // ring index of dz, or -1
+    bool imp;           // implicit dz (dx_epilogue): the layer's g read through its ReLU mask, the BN
+    const void *dzs;    //   scale applied to the weight gradient's columns and folded into W2
+    const void *w2;
+    void *dbott;
+};
+
+// Two streams: the input-gradient chain on the caller's stream (main), every write into
+// the gradient buffer on the weight-gradient stream (side), which waits for main at each
+// wgrad(): the dW GEMMs of a layer overlap the input gradients below it. Hazards (WAR on
+// shared scratch) are ordered by events: the dz / g / dbott buffers cycle three deep and
+// main waits for a step's side work before it overwrites what that work read (dx_wait,
+// side_wait). All gradient writes (and so the data-parallel
+// bucket gates, dp_issue) are on side; main joins side before returning.
+struct BackwardPass {
+    KfNet *const net;
+    void *const caller;  // the stream current at entry; every return leaves it current
+    void *mainst;
+    const bool two;
+    // With the weight-gradient stream the input-gradient chain runs on a high-priority
+    // stream (its workgroups are dispatched ahead of the weight gradients') and each weight
+    // gradient launches 256 workgroups instead of 512. Same-box A/B (bench default, 20
+    // steps, median): one stream 38.13 / 38.36 ms, two streams 37.57 / 37.52;
+    // the chain's priority is neutral (37.55 without it), 512-workgroup weight gradients
+    // cost 1.2 ms (38.78). With the row-subsampled step (r6) 160 workgroups: non-den step
+    // time 17.52 ms against 17.81 at 256, 17.57 at 128, 18.15 at 96 (same box, 3 runs each).
+    const bool hp;
+    const int old_target;
+    // Steps (layers that hand a gradient down) cycle through three dz / g / dbott buffers.
+    // Before step i rewrites its dz / g buffers, main waits for the side work of step i - 2,
+    // the last reader of what step i - 3 wrote there; before it rewrites its dbott buffer
+    // (earlier in the step), for that of step i - 3. Step i - 1's side work keeps running.
+    // The side stream is in order, so waiting for step j's event covers every step <= j.
+    int stepi = 0, waited = -1;  // side work of steps <= waited: main has waited for it
+    int flip = 0, done = 0;
+    // dbott cycles by TDNN-F / prefinal step (the steps that write it), not by layer: a
+    // pass-through step in between (Batchnorm) must not advance it, or the next step would
+    // reuse a buffer whose weight gradient may still read it (side_wait covers step i - 3).
+    int nbott = 0;
+    size_t dp_next = 0;
+    const void *dz;    // gradient w.r.t. pre-activation of the current layer
+    const void *gcur;  // stored gradient w.r.t. the current layer's output
+
+    // (the top layer must be the chain output)
+    BackwardPass(KfNet *n, const void *out_grad)
+        : net(n), caller(kf_get_stream()), mainst(caller), two(n->wg_side != 0 && n->wg_stream != nullptr),
+          hp(two && n->hp_stream), old_target(kf_gemm_wgrad_target(two ? 160 : 0)), dz(out_grad), gcur(out_grad) {}
+    ~BackwardPass() {
+        kf_gemm_wgrad_target(old_target);
+        kf_set_stream(caller);
+    }
+
+    bool to_side() {  // side continues after everything main enqueued so far
+        if (!two) return true;
+        if (kf_event_record(net->ev_go, mainst) != 0 || kf_stream_wait(net->wg_stream, net->ev_go) != 0) {
+            set_err("backward: weight-gradient stream order");
+            return false;
+        }
+        kf_set_stream(net->wg_stream);
+        if (net->stall_side > 0 && kf_debug_spin(net->wg_stream, net->stall_side) != 0) {
+            set_err("backward: debug stall");
+            return false;
+        }
+        return true;
+    }
+    void to_main() { kf_set_stream(mainst); }
+    bool side_wait(int upto) {
+        if (!two || upto <= waited || upto < 0) return true;
+        if (kf_stream_wait(mainst, net->ev_step[upto % 3]) != 0) {
+            set_err("backward: weight-gradient stream join");
+            return false;
+        }
+        waited = upto;
+        return true;
+    }
+    bool dx_wait() { return side_wait(stepi - 2); }
+    // main waits for everything on side so far
+    bool join_side() {
+        if (!two || (kf_event_record(net->ev_side, net->wg_stream) == 0 && kf_stream_wait(mainst, net->ev_side) == 0))
+            return true;
+        set_err("backward: weight-gradient stream join");
+        return false;
+    }
+    // a weight gradient: on side, after what main enqueued so far
+    template <class F>
+    bool wgrad(F &&f) {
+        if (!to_side()) return false;
+        const bool ok = f();
+        to_main();
+        return ok;
+    }
+
+    bool begin();
+    int step(int li, int ndone);  // 1: go on below, 0: nothing trainable below, -1: failed
+    bool finish();
+
+    // one function per layer kind; TDNN-F and conv split by what they launch
+    bool to_full_epilogue(Step &s), to_full_scatter(Step &s);
+    bool linear(Step &s), attention(Step &s), prefinal(Step &s), combine(Step &s), tdnnf(Step &s), conv(Step &s);
+    KfOperand masked(const Step &s, const Tdnnf &t, KfOperand o) const;
+    bool tdnnf_affine_wgrad(Step &s, const Tdnnf &t), tdnnf_affine_dgrad(Step &s, const Tdnnf &t);
+    bool tdnnf_affine_dgrad_mx(Step &s, const Tdnnf &t, const KfEpilogue &E1, void *edge);
+    bool tdnnf_linear_wgrad(Step &s, const Tdnnf &t), tdnnf_linear_dgrad(Step &s, const Tdnnf &t);
+    bool conv_small_fin(Step &s), conv_wgrad_plain(Step &s), conv_wgrad_compact(Step &s);
+    bool conv_window(Step &s, bool side);
+    bool conv_dgrad_compact(Step &s), conv_dgrad_strided(Step &s), conv_dgrad_plain(Step &s);
+};
+
+bool BackwardPass::begin() {
+    if (hp) {
+        if (kf_event_record(net->ev_go, caller) != 0 || kf_stream_wait(net->hp_stream, net->ev_go) != 0) {
+            set_err("backward: chain stream order");
+            return false;
+        }
+        mainst = net->hp_stream;
+        kf_set_stream(mainst);
+    }
+    if (!to_side()) return false;
+    for (const auto &r : net->offpath) bridge_gpu_memset(net->grad + r.first, 0, (size_t)r.second * 4);
+    // negative control of the data-parallel tests: exchanging before any producer ran
+    if (net->dp && net->dp_early) {
+        if (!dp_issue(net, dp_next, INT_MAX)) return false;
+        // ... and finished before any producer writes (deterministic: left to race with the
+        // backward, a fast one could finish first and hide the early exchange)
+        if (kf_dp_join(net->dp) != 0 ||
+            (two && (kf_event_record(net->ev_side, net->wg_stream) != 0 || kf_stream_wait(mainst, net->ev_side) != 0))) {
+            set_err("backward: early-exchange join");
+            return false;
+        }
+    }
+    to_main();
+    // the bottleneck-gradient row mask of this row set (rebuilt when the set changes, on the
+    // chain stream, which reads it): every 3-strided compact TDNN-F layer of one bottleneck
+    // width zeroes the scratch row through it
+    if (net->rs.Tc > net->rs.Tc0 && net->rowmask) {
+        int bn = 0;
+        for (size_t li = net->first_c; li < net->layers.size(); ++li) {
+            const Layer &q = net->layers[li].L;
+            if (q.type != LayerType::TDNNF || q.time_stride == 0) continue;
+            bn = bn == 0 || bn == q.bottleneck ? q.bottleneck : -1;
+        }
+        if (bn > 0 && bn % 8 == 0 && (net->rm_bn != bn || net->rm_tc0 != net->rs.Tc0 || net->rm_tc != net->rs.Tc)) {
+            bridge_gpu_memset(net->rowmask, 0xFF, (size_t)net->rs.Tc * bn / 8);
+            bridge_gpu_memset(net->rowmask + (size_t)net->rs.Tc0 * bn / 8, 0, (size_t)bn / 8);
+            net->rm_bn = bn;
+            net->rm_tc0 = net->rs.Tc0;
+            net->rm_tc = net->rs.Tc;
+        }
+    }
+    return true;
+}
+
+int BackwardPass::step(int li, int ndone) {
+    done = ndone;
+    NetLayer &nl = net->layers[li];
+    const Layer &L = nl.L;
+    // the first compact layer's input gradient: in compact rows with the input layer's
+    // mask gathered to them, then scattered to the full rows below (zero elsewhere)
+    const bool first_c = net->rs.Tc && li == net->first_c;
+    Step s{nl, li, rows_of(net, li), net->T,
+           // (the first compact layer read its input gathered to the compact rows)
+           first_c && !net->conv_c ? net->xc : act_of(net, nl.input), nl.needs_dx && nl.input >= 0, first_c,
+           net->dz[flip], net->g[flip],
+           // (this step's dbott buffer was last written at step i - 3 or earlier)
+           !two ? net->dbott : nbott % 3 == 0 ? net->dbott : nbott % 3 == 1 ? net->dbott2 : net->dbott3, KfEpilogue()};
+    if (!side_wait(stepi - 3)) return -1;
+    net->dz8_layer[flip] = -1;
+    if (s.want_dx && !dx_epilogue(net, nl.input, s.dz_next, s.g_next, s.E)) return -1;
+    if (s.want_dx && s.to_full && !to_full_epilogue(s)) return -1;
+    if (nl.bypass) {
+        s.E.resid = gcur;
+        s.E.ldr = L.out_dim;
+        s.E.resid_alpha = (float)L.bypass_scale;
+    }
+    bool ok = true;
+    switch (L.type) {
+        case LayerType::Output:
+        case LayerType::Linear: ok = linear(s); break;
+        case LayerType::Attention: ok = attention(s); break;
+        case LayerType::Prefinal: ok = prefinal(s); break;
+        case LayerType::TDNNF: ok = tdnnf(s); break;
+        case LayerType::ConvReluBN: ok = conv(s); break;
+        case LayerType::CombineFeatureMaps: ok = combine(s); break;
+        case LayerType::Batchnorm:
+            if (s.want_dx)  // dz already is the gradient at the BN input (dx_epilogue): the same
+                            // dz / gcur buffers for the layer below, no flip
+                return !net->dp || wgrad([&] { return dp_issue(net, dp_next, done); }) ? 1 : -1;
+            break;
+        case LayerType::IDCT:
+        case LayerType::SpecAugment:
+            if (s.want_dx) {
+                set_err("backward through " + L.name + " into trainable layers is not supported");
+                return -1;
+            }
+            break;
+        default:
+            set_err("backward: unsupported layer " + L.name);
+            return -1;
+    }
+    if (!ok || (s.want_dx && s.to_full && !to_full_scatter(s))) return -1;
+    // gradient buckets complete at this step go to the communication stream (their
+    // gates on side, behind the step's weight gradients)
+    if (two) kf_set_stream(net->wg_stream);
+    if (net->dp && !dp_issue(net, dp_next, done)) return -1;
+    if (two && kf_event_record(net->ev_step[stepi % 3], net->wg_stream) != 0) {
+        set_err("backward: weight-gradient stream event");
+        return -1;
+    }
+    to_main();
+    if (!s.want_dx) return 0;  // nothing trainable below
+    dz = s.dz_next;
+    gcur = s.g_next;
+    net->dz_last = s.dz_next;
+    ++stepi;
+    flip = stepi % 3;
+    return 1;
+}
+
+// the rest of the buckets, then main waits for side (SGD reads every gradient) and for
+// every bucket
+bool BackwardPass::finish() {
+    if (two) kf_set_stream(net->wg_stream);
+    if (net->dp && !dp_issue(net, dp_next, INT_MAX)) return false;
+    to_main();
+    if (!join_side()) return false;
+    if (hp) {  // the caller's stream continues after the chain (which joined side)
+        if (kf_event_record(net->ev_go, mainst) != 0 || kf_stream_wait(caller, net->ev_go) != 0) {
+            set_err("backward: chain stream join");
+            return false;
+        }
+        mainst = caller;
+        kf_set_stream(caller);
+    }
+    if (net->dp && kf_dp_join(net->dp) != 0) {
+        set_err(std::string("dp join: ") + (kf_dp_last_error() ? kf_dp_last_error() : ""));
+        return false;
+    }
+    return true;
+}
+
+// the first compact layer's input gradient goes to the compact rows (net->dzc), through the
+// input layer's mask gathered to them
+bool BackwardPass::to_full_epilogue(Step &s) {
+    KfEpilogue &E = s.E;
+    const NetLayer &pl = net->layers[s.nl.input];
+    const int w = pl.L.out_dim;
+    if (E.out || !E.out2 || E.edge_out || E.out8 || (E.mask_in && !pl.mask) || (w * 2) % 16 || (w / 8) % 16) {
+        set_err("row subsampling: unsupported input gradient into " + pl.L.name);
+        return false;
+    }
+    if (E.mask_in && !net->conv_c) {  // (a compact conv's mask already is in compact rows)
+        if (!ck(kf_gather_rows(net->mc, pl.mask, w / 8, s.Tfull, net->rs.Tc0, net->rs.Tc), "row set mask gather")) return false;
+        E.mask_in = net->mc;
+    }
+    E.out2 = net->dzc;
+    return true;
+}
+bool BackwardPass::to_full_scatter(Step &s) {
+    const int w = net->layers[s.nl.input].L.out_dim;
+    if (!net->conv_c)
+        return ck(kf_scatter_rows(s.dz_next, net->dzc, (long long)w * 2, s.Tfull, net->rs.Tc0, net->rs.Tc), "row set scatter");
+    // the conv below reads the compact rows (net->dzc); only its tail window (full rows
+    // from window_t0, conv_window) takes the scattered form
+    const int r0 = net->rs.window_t0;
+    return net->rs.nt == 0 || ck(kf_scatter_rows_from((char *)s.dz_next + (size_t)r0 * w * 2, net->dzc, (long long)w * 2,
+                                                      s.Tfull, net->rs.Tc0, net->rs.Tc, r0),
+                                 "row set scatter (tail window)");
+}
+
+bool BackwardPass::linear(Step &s) {
+    NetLayer &nl = s.nl;
+    const int T = s.T, din = nl.L.in_dim, dout = nl.L.out_dim;
+    KfOperand A = op_base(s.x, din, T, din, 0);
+    KfOperand B = op_base(dz, dout, T, dout, 0);
+    if (!wgrad([&] { return ck(kf_gemm_wgrad(din, dout, T, &A, &B, gptr(net, nl.pW), dout, gptr(net, nl.pb), 0), "wgrad"); }))
+        return false;
+    if (!s.want_dx) return true;
+    KfOperand A2 = op_base(dz, dout, T, dout, 1);
+    KfOperand B2 = op_base(wptr(net, nl.pW), dout, din, dout, 1);
+    return dx_wait() && ck(kf_gemm_fused(T, din, dout, &A2, &B2, &s.E), "dgrad");
+}
+
+// dz = gradient at the attention output (pre-ReLU, from dx_epilogue); exact attention
+// backward into d(affine output), then the affine's weight / bias / input gradients
+bool BackwardPass::attention(Step &s) {
+    NetLayer &nl = s.nl;
+    const int T = s.T, din = nl.L.in_dim, A = att_affine(nl.L);
+    KfAttention att = att_args(nl, T);
+    if (!ck(kf_attention_backward(&att, dz, nl.L.out_dim, nl.dproj, nl.att_scratch), "attention backward")) return false;
+    KfOperand Aw = op_base(s.x, din, T, din, 0);
+    KfOperand Bw = op_base(nl.dproj, A, T, A, 0);
+    if (!wgrad([&] {
+            return ck(kf_gemm_wgrad(din, A, T, &Aw, &Bw, gptr(net, nl.pW), A, gptr(net, nl.pb), 0), "attention wgrad");
+        }))
+        return false;
+    if (!s.want_dx) return true;
+    KfOperand A2 = op_base(nl.dproj, A, T, A, 1);
+    KfOperand B2 = op_base(wptr(net, nl.pW), A, din, A, 1);
+    return dx_wait() && ck(kf_gemm_fused(T, din, A, &A2, &B2, &s.E), "attention dgrad");
+}
+
+// dz = gradient at the small (BN2) pre-activation
+bool BackwardPass::prefinal(Step &s) {
+    NetLayer &nl = s.nl;
+    const int T = s.T, din = nl.L.in_dim, big = nl.L.big_dim, small = nl.L.small_dim;
+    KfOperand A = op_base(nl.aux, big, T, big, 0);
+    KfOperand B = op_base(dz, small, T, small, 0);
+    if (!wgrad([&] {
+            return ck(kf_gemm_wgrad(big, small, T, &A, &B, gptr(net, nl.pW2), small, nullptr, 0), "prefinal small wgrad");
+        }))
+        return false;
+    void *dzbig = s.dbott_buf;
+    net->dbott_last = dzbig;
+    ++nbott;
+    KfEpilogue E1 = epi0();
+    E1.out2 = dzbig;
+    E1.ldo2 = big;
+    E1.scale2 = nl.bn_scale;
+    E1.mask_in = nl.mask;
+    KfOperand A1 = op_base(dz, small, T, small, 1);
+    KfOperand B1 = op_base(wptr(net, nl.pW2), small, big, small, 1);
+    if (!ck(kf_gemm_fused(T, big, small, &A1, &B1, &E1), "prefinal small dgrad")) return false;
+    KfOperand A3 = op_base(s.x, din, T, din, 0);
+    KfOperand B3 = op_base(dzbig, big, T, big, 0);
+    if (!wgrad([&] {
+            return ck(kf_gemm_wgrad(din, big, T, &A3, &B3, gptr(net, nl.pW), big, gptr(net, nl.pb), 0), "prefinal big wgrad");
+        }))
+        return false;
+    if (!s.want_dx) return true;
+    KfOperand A4 = op_base(dzbig, big, T, big, 1);
+    KfOperand B4 = op_base(wptr(net, nl.pW), big, din, big, 1);
+    return dx_wait() && ck(kf_gemm_fused(T, din, big, &A4, &B4, &s.E), "prefinal big dgrad");
+}
+
+bool BackwardPass::combine(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    if (nl.input2 >= 0 && net->layers[nl.input2].needs_dx + is_trainable(net->layers[nl.input2].L.type)) {
+        // the ivector branch: sum the broadcast columns per sequence, then back
+        // through its batchnorm-component(s) and linear-component (B rows)
+        if (!net->layers[nl.input2].per_seq) {
+            set_err("combine " + L.name + ": gradient into a frame-level second input not supported");
+            return false;
+        }
+        const int wb = L.height * L.nf2, rowsB = net->B;
+        if (!ck(kf_combine_feature_maps_backward(dz, L.out_dim, net->seq_off, rowsB, nl.gdb, wb, L.height, L.nf1, L.nf2),
+                "combine backward"))
+            return false;
+        for (int cur = nl.input2; cur >= 0; cur = net->layers[cur].input) {
+            NetLayer &q = net->layers[cur];
+            const int qd = q.L.out_dim;
+            if (q.L.type == LayerType::Batchnorm) {
+                if (!ck(kf_scale_cols(nl.gdb, qd, q.bn_scale, nl.gdb, qd, rowsB, qd), "ivector bn backward")) return false;
+            } else if (q.L.type == LayerType::Linear) {
+                if (!wgrad([&] {
+                        return ck(kf_rows_wgrad(act_of(net, q.input), q.L.in_dim, nl.gdb, qd, gptr(net, q.pW), qd, rowsB,
+                                                q.L.in_dim, qd),
+                                  "ivector linear wgrad");
+                    }))
+                    return false;
+                if (q.input >= 0) {
+                    set_err("ivector branch: a linear-component below another one is not supported");
+                    return false;
+                }
+            } else {
+                set_err("ivector branch: unsupported layer " + q.L.name);
+                return false;
+            }
+        }
+    }
+    if (nl.needs_dx && nl.input >= 0 && net->layers[nl.input].needs_dx + is_trainable(net->layers[nl.input].L.type)) {
+        set_err("backward through " + L.name + " into a trainable frame-level input is not supported");
+        return false;
+    }
+    s.want_dx = false;
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// TDNN-F
+// ---------------------------------------------------------------------------
+bool BackwardPass::tdnnf(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    const int st = nl.compact && net->rs.Tc ? L.time_stride / 3 : L.time_stride, np = st > 0 ? 2 : 1;
+    const int ib = dz_index(net, dz);
+    const bool imp = ib >= 0 && net->dz_imp[ib];
+    Tdnnf t{st, L.bottleneck, np * L.in_dim, np * L.bottleneck, ib, imp, imp ? gcur : dz, nullptr, nullptr};
+    // The affine weight gradients run on the weight-gradient stream. (r5, with a
+    // two-deep gradient ring, every other one ran on the chain: the chain waited for
+    // the side stream before each linear input gradient, and that balanced the two,
+    // 36.66 / 36.89 -> 36.55 / 36.65 ms. With the three-deep ring, all on side: 24.81 /
+    // 24.89 against 24.96 / 25.13 ms every other, 25.51 / 25.69 all on the chain.)
+    // nnet_debug_backward: 1 = every other on the chain, 2 = all on the chain (tests).
+    const bool aff_on_main = two && (net->main_aff == 2 || (net->main_aff == 1 && (done & 1)));
+    if (!aff_on_main && !wgrad([&] { return tdnnf_affine_wgrad(s, t); })) return false;
+    t.w2 = wptr(net, nl.pW2);
+    if (t.imp) {
+        if (!ck(kf_scale_cols(t.w2, L.out_dim, nl.bn_scale, net->w2s, L.out_dim, t.kaff, L.out_dim), "tdnnf scaled W2"))
+            return false;
+        t.w2 = net->w2s;
+    }
+    t.dbott = s.dbott_buf;
+    net->dbott_last = t.dbott;
+    ++nbott;
+    if (!tdnnf_affine_dgrad(s, t) || (aff_on_main && !tdnnf_affine_wgrad(s, t))) return false;
+    if (!wgrad([&] { return tdnnf_linear_wgrad(s, t); })) return false;
+    return !s.want_dx || (dx_wait() && tdnnf_linear_dgrad(s, t));
+}
+
+KfOperand BackwardPass::masked(const Step &s, const Tdnnf &t, KfOperand o) const {
+    if (t.imp) {
+        o.mask = s.nl.mask;
+        o.mask_rows = s.T;
+    }
+    return o;
+}
+
+// affine weight / bias gradient: splice+(bott)^T . dz
+bool BackwardPass::tdnnf_affine_wgrad(Step &s, const Tdnnf &t) {
+    NetLayer &nl = s.nl;
+    const int T = s.T, dout = nl.L.out_dim;
+    KfOperand A = t.s > 0 ? op_splice(nl.aux, T, t.bn, 0, t.s, KF_CLAMP, 0) : op_base(nl.aux, t.bn, T, t.bn, 0);
+    KfOperand B = masked(s, t, op_base(t.dzs, dout, T, dout, 0));
+    if (t.imp)
+        return ck(kf_gemm_wgrad_scaled(t.kaff, dout, T, &A, &B, gptr(net, nl.pW2), dout, gptr(net, nl.pb2), 0, nl.bn_scale),
+                  "tdnnf affine wgrad");
+    return ck(kf_gemm_wgrad(t.kaff, dout, T, &A, &B, gptr(net, nl.pW2), dout, gptr(net, nl.pb2), 0), "tdnnf affine wgrad");
+}
+
+// bottleneck gradient: transpose of the [0, +s] clamped splice
+bool BackwardPass::tdnnf_affine_dgrad(Step &s, const Tdnnf &t) {
+    NetLayer &nl = s.nl;
+    const int T = s.T, dout = nl.L.out_dim, bn = t.bn;
+    KfEpilogue E1 = epi0();
+    E1.out = t.dbott;
+    E1.ldo = bn;
+    // compact rows with a tail: the scratch row Tc0 read row Tc0 - 1's gradient
+    // through the +1 adjacency; its true gradient is zero (written as zero through
+    // the row mask)
+    bool zero_scratch = nl.compact && net->rs.Tc > net->rs.Tc0 && t.s > 0;
+    if (zero_scratch && net->rowmask && net->rm_bn == bn && net->rm_tc0 == net->rs.Tc0 && net->rm_tc == net->rs.Tc) {
+        E1.out = nullptr;
+        E1.out2 = t.dbott;
+        E1.ldo2 = bn;
+        E1.mask_in = net->rowmask;
+        zero_scratch = false;
+    }
+    if (t.s == 0) {
+        KfOperand A1 = masked(s, t, op_base(t.dzs, dout, T, dout, 1));
+        KfOperand B1 = op_base(t.w2, dout, bn, dout, 1);
+        return ck(kf_gemm_fused(T, bn, dout, &A1, &B1, &E1), "tdnnf affine dgrad");
+    }
+    if (s.want_dx) {
+        // the linear input gradient's edge row (row T of dbott: sum of rows 0 .. s),
+        // summed by this GEMM's first row tile
+        E1.edge_out = (char *)t.dbott + (size_t)T * bn * 2;
+        E1.edge_r0 = 0;
+        E1.edge_r1 = t.s + 1 < T ? t.s + 1 : T;
+        E1.edge_src = E1.out2 ? 1 : 0;
+    }
+    // spare row T of dz (of g when dz is implicit: the masked sum) holds
+    // sum_{t >= T-1-s} dz[t] (clamped-splice transpose)
+    void *edge = (char *)t.dzs + (size_t)T * dout * 2;
+    const bool have_edge = !t.imp && t.ib >= 0 && net->dz_edge[t.ib];  // dx_epilogue's
+    if (nl.compact && net->rs.Tc) {
+        // compact rows: the source rows T-1-3 .. T-1 that are in the set, in
+        // source order (the others carry no gradient)
+        int rows[4], nr = 0;
+        for (int f = std::max(0, s.Tfull - 1 - nl.L.time_stride); f < s.Tfull; ++f) {
+            const int c = net->rs.compact_of(f);
+            if (c >= 0 && nr < 4) rows[nr++] = c;
+        }
+        if (!ck(kf_rows_sum_list(edge, t.dzs, dout, rows, nr, dout), "row set edge")) return false;
+    } else if (!have_edge && !ck(kf_rows_sum_mask(edge, t.dzs, dout, T - 1 - t.s < 0 ? 0 : T - 1 - t.s, T, dout,
+                                                  t.imp ? nl.mask : nullptr),
+                                 "edge"))
+        return false;
+    if (net->fp8 && t.ib >= 0 && net->dz8_layer[t.ib] == s.li && T > 1) return tdnnf_affine_dgrad_mx(s, t, E1, edge);
+    KfOperand A1 = masked(s, t, op_splice(t.dzs, T, dout, 0, -t.s, KF_ZERO, 1));
+    A1.edge_t[1] = T - 1;
+    A1.edge_row[1] = T;
+    KfOperand B1 = op_wrows(t.w2, 2, bn, dout);
+    if (!ck(kf_gemm_fused(T, bn, 2 * dout, &A1, &B1, &E1), "tdnnf affine dgrad")) return false;
+    if (zero_scratch)  // (no row mask for this bottleneck width)
+        bridge_gpu_memset((char *)t.dbott + (size_t)net->rs.Tc0 * bn * 2, 0, (size_t)bn * 2);
+    return true;
+}
+
+// MXFP8 (the one MFMA-bound backward product, K = 2 x dout): rows 0 .. T-2 from dz's e4m3
+// copy [dz(t) | dz(t-s)] against the e4m3 weight rows; row T-1, whose second part is the
+// clamped-edge sum, again in fp16 (the MXFP8 operand has no edge rows)
+bool BackwardPass::tdnnf_affine_dgrad_mx(Step &s, const Tdnnf &t, const KfEpilogue &E1, void *edge) {
+    NetLayer &nl = s.nl;
+    const int T = s.T, dout = nl.L.out_dim, bn = t.bn;
+    const Mx &d8 = net->dz8[t.ib];
+    const int pw = pad128(dout);
+    KfOperand A1 = op_base(d8.q, d8.ld, T, 2 * pw, 1);
+    A1.nparts = 2;
+    A1.part_width = pw;
+    A1.dt[1] = -t.s;
+    A1.tpolicy = KF_ZERO;
+    A1.fmt = KF_FMT_MXFP8;
+    A1.scales = d8.s;
+    A1.lds = d8.ld / 32;
+    KfOperand B8 = op_mxw(nl.w8d, bn);
+    // rows 0 .. T-2, and row T-1 by the last row tile's workgroups
+    return ck(kf_gemm_fused_edge(T - 1, bn, 2 * pw, &A1, &B8, &E1, (char *)t.dbott + (size_t)(T - 1) * bn * 2,
+                                 (const char *)dz + (size_t)(T - 1) * dout * 2, edge, wptr(net, nl.pW2), dout),
+              "tdnnf affine dgrad mxfp8");
+}
+
+// linear weight gradient: splice-(x)^T . dbott
+bool BackwardPass::tdnnf_linear_wgrad(Step &s, const Tdnnf &t) {
+    const int T = s.T, din = s.nl.L.in_dim;
+    KfOperand A2 = t.s > 0 ? op_splice(s.x, T, din, -t.s, 0, KF_CLAMP, 0) : op_base(s.x, din, T, din, 0);
+    KfOperand B2 = op_base(t.dbott, t.bn, T, t.bn, 0);
+    return ck(kf_gemm_wgrad(t.klin, t.bn, T, &A2, &B2, gptr(net, s.nl.pW), t.bn, nullptr, 0), "tdnnf linear wgrad");
+}
+
+// input gradient: transpose of the [-s, 0] clamped splice
+bool BackwardPass::tdnnf_linear_dgrad(Step &s, const Tdnnf &t) {
+    const int T = s.T, din = s.nl.L.in_dim, bn = t.bn;
+    if (t.s > 0) {
+        // spare row T of dbott holds sum_{t <= s} dbott[t]
+        // (row T of dbott: the affine input gradient's epilogue summed it, E1)
+        KfOperand A3 = op_splice(t.dbott, T, bn, t.s, 0, KF_ZERO, 1);
+        A3.edge_t[0] = 0;
+        A3.edge_row[0] = T;
+        KfOperand B3 = op_wrows(wptr(net, s.nl.pW), 2, din, bn);
+        return ck(kf_gemm_fused(T, din, 2 * bn, &A3, &B3, &s.E), "tdnnf linear dgrad");
+    }
+    KfOperand A3 = op_base(t.dbott, bn, T, bn, 1);
+    KfOperand B3 = op_base(wptr(net, s.nl.pW), bn, din, bn, 1);
+    return ck(kf_gemm_fused(T, din, bn, &A3, &B3, &s.E), "tdnnf linear dgrad");
+}
+
+// ---------------------------------------------------------------------------
+// conv-relu-batchnorm
+// ---------------------------------------------------------------------------
+bool BackwardPass::conv(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    const bool compact = conv_compact(net, s.li);
+    // compact-row conv: the tail window runs first, on the weight-gradient stream beside
+    // the residue GEMMs (conv_window)
+    if (s.want_dx && compact && net->rs.nt > 0 && two && s.E.out2 && !conv_window(s, true)) return false;
+    if (nl.kp) return conv_small_fin(s);
+    if (L.fin == 1) {
+        if (!wgrad([&] {
+                return ck(kf_conv_c1_wgrad(s.T, L.hin, L.hout, L.hsub, L.fout, (int)nl.dt.size(), nl.dt.data(),
+                                           nl.dh.data(), s.x, dz, gptr(net, nl.pW), gptr(net, nl.pb)),
+                          "conv c1 wgrad");
+            }))
+            return false;
+    } else if (!wgrad([&] { return compact ? conv_wgrad_compact(s) : conv_wgrad_plain(s); })) {
+        return false;
+    }
+    if (!s.want_dx) return true;
+    if (!dx_wait()) return false;
+    if (L.fin == 1) {
+        set_err("conv " + L.name + ": input gradient of a 1-filter conv not supported");
+        return false;
+    }
+    if (compact) return conv_dgrad_compact(s);
+    if (L.hsub > 1 && L.hin % L.hsub == 0 && !s.E.out) return conv_dgrad_strided(s);
+    return conv_dgrad_plain(s);
+}
+
+// small fin: the forward's im2col is still in nl.im2col
+bool BackwardPass::conv_small_fin(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    const int T = s.T, noff = (int)nl.dt.size(), K = noff * L.fin;
+    KfEpilogue &E = s.E;
+    // wgrad over the padded K (the pad columns are zero), then the first
+    // ntaps*fin rows into the flat gradient
+    KfOperand A = op_base(nl.im2col, nl.kp, T * L.hout, nl.kp, 0);
+    KfOperand B = op_base(dz, L.fout, T * L.hout, L.fout, 0);
+    if (!wgrad([&] {
+            return ck(kf_gemm_wgrad(nl.kp, L.fout, T * L.hout, &A, &B, nl.gwpad, L.fout, gptr(net, nl.pb), 0),
+                      "conv small-fin wgrad") &&
+                   ck(ops_copy(gptr(net, nl.pW), nl.gwpad, 2 * K * L.fout), "conv small-fin wgrad copy");
+        }))
+        return false;
+    if (!s.want_dx) return true;
+    // the input gradient overwrites nl.im2col, which the weight gradient
+    // just read on side: main waits for side here
+    if (!join_side()) return false;
+    waited = stepi - 1;
+    if (E.out || E.mask_in || E.scale2 || !E.out2) {
+        set_err("conv " + L.name + ": small-fin input gradient only into combine-feature-maps");
+        return false;
+    }
+    // dP = dz . Wpad^T into the im2col buffer, then the gather col2im
+    KfOperand A2 = op_base(dz, L.fout, T * L.hout, L.fout, 1);
+    KfOperand B2 = op_base(nl.wpad, L.fout, nl.kp, L.fout, 1);
+    KfEpilogue Ed = epi0();
+    Ed.out = nl.im2col;
+    Ed.ldo = nl.kp;
+    return ck(kf_gemm_fused(T * L.hout, nl.kp, L.fout, &A2, &B2, &Ed), "conv small-fin dgrad") &&
+           ck(kf_col2im_small(nl.im2col, T, L.hin, L.hout, L.hsub, L.fin, noff, nl.dt.data(), nl.dh.data(), nl.kp, E.out2,
+                              L.in_dim),
+              "col2im small");
+}
+
+bool BackwardPass::conv_wgrad_plain(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    KfOperand A = op_im2col(nl, s.x, s.T, 0);
+    KfOperand B = op_base(dz, L.fout, s.T * L.hout, L.fout, 0);
+    return ck(kf_gemm_wgrad((int)nl.dt.size() * L.fin, L.fout, s.T * L.hout, &A, &B, gptr(net, nl.pW), L.fout,
+                            gptr(net, nl.pb), 0),
+              "conv wgrad");
+}
+
+// output gradient on the compact rows only (net->dzc): the reduction over
+// output frames 3c (c < Tc0), then over the tail frames, added
+bool BackwardPass::conv_wgrad_compact(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    const RowSet &rs = net->rs;
+    const int K = (int)nl.dt.size() * L.fin;
+    KfOperand A = op_im2col(nl, s.x, s.T, 0);
+    A.tmul = 3;
+    A.nrows = rs.Tc0 * L.hout;
+    KfOperand B = op_base(net->dzc, L.fout, rs.Tc0 * L.hout, L.fout, 0);
+    if (!ck(kf_gemm_wgrad(K, L.fout, rs.Tc0 * L.hout, &A, &B, gptr(net, nl.pW), L.fout, gptr(net, nl.pb), 0),
+            "conv wgrad (compact rows)"))
+        return false;
+    if (rs.nt == 0) return true;
+    A.t0 = rs.tail_t0;
+    A.nrows = rs.nt * L.hout;
+    B.base = (const char *)net->dzc + (size_t)rs.Tc0 * L.hout * L.fout * 2;
+    B.nrows = B.T = rs.nt * L.hout;
+    return ck(kf_gemm_wgrad(K, L.fout, rs.nt * L.hout, &A, &B, gptr(net, nl.pW), L.fout, gptr(net, nl.pb), 1),
+              "conv wgrad (compact tail rows)");
+}
+
+// compact-row conv: the input gradient of the frames the tail reaches (window_t0 ...) comes
+// from the full-row kernel on a window of the scattered output gradient dz (zero below it).
+// side = true: on the weight-gradient stream; main joins it after the residue GEMMs.
+bool BackwardPass::conv_window(Step &s, bool side) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    const int noff = (int)nl.dt.size(), w0 = net->rs.window_t0, tw = s.T - w0;
+    KfOperand A2 = op_col2im(nl, (const char *)dz + (long long)w0 * L.hout * L.fout * 2, tw);
+    KfOperand B2 = op_wrows(wptr(net, nl.pW), noff, L.fin, L.fout);
+    KfEpilogue Ew = at_frame(s.E, L, w0);
+    auto window = [&] { return ck(kf_gemm_fused(tw * L.hin, L.fin, noff * L.fout, &A2, &B2, &Ew), "conv dgrad (tail window)"); };
+    if (!side) return window();
+    return to_side() && side_launch(net, mainst, "backward: conv window", window);
+}
+
+// The output gradient is non-zero on the compact frames only (net->dzc): input frame
+// f = 3c + e receives only the taps with dt = e, from compact frame c. One GEMM per residue
+// e over those taps, its rows written to frames 3c + e in place (grouped epilogue rows);
+// every nonzero term in the full-row kernel's order, so the result is bit-identical. The
+// frames the tail reaches take the full-row kernel (conv_window): on the weight-gradient
+// stream it went first, at the start of this step, and main joins it after the residues.
+bool BackwardPass::conv_dgrad_compact(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    const KfEpilogue &E = s.E;
+    const RowSet &rs = net->rs;
+    if (!E.out2 || E.out8 || E.edge_out || E.resid || E.beta != 0.f) {
+        set_err("row subsampling: unsupported input gradient of " + L.name);
+        return false;
+    }
+    const int noff = (int)nl.dt.size();
+    const long long fo = (long long)L.hout * L.fout;
+    if (rs.nt > 0 && !two && !conv_window(s, false)) return false;
+    for (int e = -1; e <= 1; ++e) {
+        const int c_hi = std::min(rs.Tc0, (rs.residue_last_frame - e) / 3 + 1), c_lo = e < 0 ? 1 : 0;
+        if (c_hi <= c_lo) continue;
+        KfOperand A2 = op_col2im(nl, (const char *)net->dzc + c_lo * fo * 2, c_hi - c_lo);
+        KfOperand B2 = op_wrows(wptr(net, nl.pW), noff, L.fin, L.fout);
+        int np = 0;
+        for (int o = 0; o < noff; ++o) {
+            if (nl.dt[o] != e) continue;
+            A2.dt[np] = 0;
+            A2.dh[np] = -nl.dh[o];
+            B2.dt[np] = o * L.fin;
+            ++np;
+        }
+        A2.nparts = B2.nparts = np;
+        A2.ncols = B2.ncols = np * L.fout;
+        KfEpilogue Er = at_frame(E, L, 3LL * c_lo + e);
+        Er.row_group = L.hin;
+        Er.row_stride = 3 * L.hin;
+        if (!ck(kf_gemm_fused((c_hi - c_lo) * L.hin, L.fin, np * L.fout, &A2, &B2, &Er), "conv dgrad (compact rows)"))
+            return false;
+    }
+    return !(rs.nt > 0 && two) || aux_join(net, mainst, "backward: conv window");
+}
+
+// strided conv: input row h' = hsub*j + pi only receives the taps with (pi - dh) % hsub == 0,
+// so one GEMM per residue pi skips the (hsub-1)/hsub of the K range the plain col2im reads
+// as zeros
+bool BackwardPass::conv_dgrad_strided(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    const KfEpilogue &E = s.E;
+    const int T = s.T, noff = (int)nl.dt.size(), hs = L.hsub;
+    // every residue's taps, residue by residue: pi's are taps[first[pi] .. first[pi + 1])
+    std::vector<int> taps, first(hs + 1, 0);
+    for (int pi = 0; pi < hs; ++pi) {
+        for (int o = 0; o < noff; ++o)
+            if (!((((pi - nl.dh[o]) % hs) + hs) % hs)) taps.push_back(o);
+        first[pi + 1] = (int)taps.size();
+    }
+    const bool twt = dgrad_wt_on();
+    char *wt = nullptr;
+    if (twt && !(wt = (char *)dgrad_wt(net, nl, taps))) {
+        set_err("conv dgrad (strided): transposed weights of " + L.name);
+        return false;
+    }
+    for (int pi = 0; pi < hs; ++pi) {
+        const int np = first[pi + 1] - first[pi];
+        if (!np) continue;
+        KfOperand A2 = op_col2im(nl, dz, T);
+        KfOperand B2 = op_wrows(wptr(net, nl.pW), noff, L.fin, L.fout);
+        for (int i = 0; i < np; ++i) {
+            const int o = taps[first[pi] + i];
+            A2.dt[i] = -nl.dt[o];
+            A2.dh[i] = (pi - nl.dh[o]) / hs;  // exact: a multiple of hsub
+            B2.dt[i] = o * L.fin;
+        }
+        A2.nparts = B2.nparts = np;
+        A2.ncols = B2.ncols = np * L.fout;
+        if (twt) B2 = op_base(wt + (size_t)first[pi] * L.fin * L.fout * 2, L.fin, np * L.fout, L.fin, 0);
+        A2.hout = L.hin / hs;
+        A2.hmul = 1;
+        A2.hdiv = 1;
+        A2.nrows = T * A2.hout;
+        KfEpilogue Ep = E;  // rows hsub*m + pi of the [(t,h) x fin] gradient
+        Ep.out2 = (char *)E.out2 + (size_t)pi * L.fin * 2;
+        Ep.ldo2 = (long long)hs * L.fin;
+        if (E.mask_in) Ep.mask_in = E.mask_in + (size_t)pi * L.fin / 8;
+        if (!ck(kf_gemm_fused(T * A2.hout, L.fin, np * L.fout, &A2, &B2, &Ep), "conv dgrad (strided)")) return false;
+    }
+    return true;
+}
+
+bool BackwardPass::conv_dgrad_plain(Step &s) {
+    NetLayer &nl = s.nl;
+    const Layer &L = nl.L;
+    KfEpilogue &E = s.E;
+    const int noff = (int)nl.dt.size();
+    KfOperand A2 = op_col2im(nl, dz, s.T);
+    KfOperand B2 = op_wrows(wptr(net, nl.pW), noff, L.fin, L.fout);
+    if (dgrad_wt_on()) {
+        std::vector<int> taps(noff);
+        for (int o = 0; o < noff; ++o) taps[o] = o;
+        void *wt = dgrad_wt(net, nl, taps);
+        if (!wt) {
+            set_err("conv dgrad: transposed weights of " + L.name);
+            return false;
+        }
+        B2 = op_base(wt, L.fin, noff * L.fout, L.fin, 0);
+    }
+    E.ldo2 = L.fin;  // dz of the input conv layer viewed as [(t,h) x fin]
+    if (E.out) E.ldo = L.fin;
+    return ck(kf_gemm_fused(s.T * L.hin, L.fin, noff * L.fout, &A2, &B2, &E), "conv dgrad");
+}
+
+int backward_impl(KfNet *net, const void *out_grad, int max_layers) {
+    if (!on_device(net, "backward")) return -1;
+    if (net->T <= 0) {
+        set_err("backward before forward");
+        return -1;
+    }
+    BackwardPass pass(net, out_grad);
+    if (!pass.begin()) return -1;
+    for (int li = net->chain_out, done = 0; li >= 0 && done < max_layers; li = net->layers[li].input, ++done) {
+        const int r = pass.step(li, done);
+        if (r < 0) return -1;
+        if (r == 0) break;
+    }
+    return pass.finish() ? 0 : -1;
+}
+
+}  // namespace
+
+extern "C" int nnet_backward(KfNet *net, const void *out_grad) {
+    kf_take_pending(__func__);
+    return backward_impl(net, out_grad, 1 << 30);
+}
+// debugging / tests: back-propagate through the top `n` layers only
+extern "C" int nnet_backward_n(KfNet *net, const void *out_grad, int n) { return backward_impl(net, out_grad, n); }
+// debugging / tests: device pointers of internal tensors
+extern "C" const void *nnet_debug_tensor(KfNet *net, const char *what, int layer) {
+    std::string w = what;
+    if (w == "dzlast") return net->dz_last;
+    for (int i = 0; i < 3; ++i) {
+        if (w == "dz" + std::to_string(i)) return net->dz[i];
+        if (w == "g" + std::to_string(i)) return net->g[i];
+    }
+    if (w == "dbott") return net->dbott_last ? net->dbott_last : net->dbott;
+    // the MXFP8 copies of dz[layer] (layer = buffer 0 / 1) and the layer whose affine input
+    // gradient reads it (as an int, through the pointer's low bits: -1 none), MXFP8 train step
+    if ((w == "dz8q" || w == "dz8s" || w == "dz8layer") && layer >= 0 && layer <= 2) {
+        if (w == "dz8layer") return (const void *)(intptr_t)(net->dz8_layer[layer] + 1);
+        return w == "dz8q" ? (const void *)net->dz8[layer].q : (const void *)net->dz8[layer].s;
+    }
+    if (layer < 0 || layer >= (int)net->layers.size()) return nullptr;
+    if (w == "aux") return net->layers[layer].aux;
+    if (w == "dproj") return net->layers[layer].dproj;
+    if (w == "mask") return net->layers[layer].mask;
+    if (w == "bn_scale") return net->layers[layer].bn_scale;
+    if (w == "bn2_scale") return net->layers[layer].bn2_scale;
+    // the e4m3 affine weight rows of the MXFP8 input gradient, [bn x 2*pad128(out)]
+    if (w == "w8dq") return net->layers[layer].w8d.q;
+    if (w == "w8ds") return net->layers[layer].w8d.s;
+    // the MXFP8 copy this layer's GEMM reads (e4m3 [T x pad128(in)], E8M0 [T x pad128(in)/32])
+    if (w == "x8q" || w == "x8s") {
+        const Mx *m = in8(net, net->layers[layer]);
+        return !m ? nullptr : w == "x8q" ? (const void *)m->q : (const void *)m->s;
+    }
+    return nullptr;
+}

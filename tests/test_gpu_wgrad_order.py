@@ -6,7 +6,7 @@ per-stream split-K slabs of kf_workspace_stream). test_gpu_nnet's
 test_wgrad_stream_bit_identical can only catch a missing order when the timing happens
 to expose it. Here nnet_debug_backward stalls the weight-gradient stream with a spin
 kernel before each of its batches of work, so it runs far behind the chain, for each
-placement of the TDNN-F affine weight gradients (KF_BWD_MAIN_AFF 0 / 1 / 2), and every
+placement of the TDNN-F affine weight gradients (nnet_debug_backward main_aff 0 / 1 / 2), and every
 gradient and the next step's output must still be bit-identical to the one-stream order.
 """
 import numpy as np
