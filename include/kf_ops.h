@@ -224,7 +224,7 @@ int kf_bn_apply(const void *x, void *y, long long rows, int D, const float *scal
 int kf_conv_c1_forward(int T, int hin, int hout, int sub, int fout, int noff, const int *dt,
                        const int *dh, const void *x, const void *W, const void *bias,
                        const float *scale, const float *shift, void *y, uint8_t *mask);
-/* its weight / bias gradient (fp32, overwritten), deterministic */
+/* its weight / bias gradient (fp32, overwritten; zeros for T <= 0), deterministic */
 int kf_conv_c1_wgrad(int T, int hin, int hout, int sub, int fout, int noff, const int *dt,
                      const int *dh, const void *x, const void *dz, float *dW, float *db);
 /* one-launch SGD over a flat parameter set: v = mom*v + g; w32 -= lr*v; w16 = rne(w32) */
@@ -233,6 +233,8 @@ int kf_sgd_flat(float *w32, void *w16, const float *g, float *v, float lr, float
 int kf_f32_to_f16_flat(const float *src, void *dst, long long n);
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.
+ * Every source row must exist: 3(tc0-1) <= T-1 and, with a tail (tc > tc0), its lowest row
+ * (T-1) - 3(tc-tc0-1) >= 0 (tail rows may lie between head rows); anything else returns -1.
  * gather: dst[c] = src[row(c)] for c < tc; scatter: every full row t < T of dst gets the
  * compact row of src whose source row is t, or zeros */
 int kf_gather_rows(void *dst, const void *src, long long row_bytes, int T, int tc0, int tc);

@@ -254,8 +254,13 @@ __global__ void k_sgd_flat(float *w32, h16 *w16, const float *g, float *v, float
          i += (long long)gridDim.x * blockDim.x) {
         const float vv = mom * v[i] + g[i];
         v[i] = vv;
-        w32[i] -= lr * vv;
-        w16[i] = f2h(w32[i]);
+        // w16 = rne(the stored fp32 w), as the vector body: without the barrier hipcc folds the
+        // update into v_fma_mixlo_f16, which rounds the exact w - lr*v to fp16 once and differs
+        // from rne(w32) at near-ties
+        float w = w32[i] - lr * vv;
+        asm volatile("" : "+v"(w));
+        w32[i] = w;
+        w16[i] = f2h(w);
     }
 }
 
@@ -304,7 +309,7 @@ int kf_conv_c1_forward(int T, int hin, int hout, int sub, int fout, int noff, co
                        const int *dh, const void *x, const void *W, const void *bias,
                        const float *scale, const float *shift, void *y, uint8_t *mask) {
     kf_take_pending(__func__);
-    if (noff > 9 || fout % 8 || fout > 256 || 256 % (fout / 8) ||
+    if (noff < 0 || noff > 9 || fout < 8 || fout % 8 || fout > 256 || 256 % (fout / 8) ||
         (long long)T * hout * fout >= (1LL << 31)) {
         lay_set_error("conv_c1_forward: noff=%d fout=%d T*hout=%lld unsupported", noff, fout,
                       (long long)T * hout);
@@ -338,7 +343,7 @@ int kf_conv_c1_forward(int T, int hin, int hout, int sub, int fout, int noff, co
 int kf_conv_c1_wgrad(int T, int hin, int hout, int sub, int fout, int noff, const int *dt,
                      const int *dh, const void *x, const void *dz, float *dW, float *db) {
     kf_take_pending(__func__);
-    if (noff > 9 || fout % 8 || fout > 256 || 256 % (fout / 8) ||
+    if (noff < 0 || noff > 9 || fout < 8 || fout % 8 || fout > 256 || 256 % (fout / 8) ||
         (long long)T * hout * fout >= (1LL << 31)) {
         lay_set_error("conv_c1_wgrad: noff=%d fout=%d T*hout=%lld unsupported", noff, fout,
                       (long long)T * hout);
@@ -348,6 +353,15 @@ int kf_conv_c1_wgrad(int T, int hin, int hout, int sub, int fout, int noff, cons
     for (int i = 0; i < noff; ++i) {
         c.dt[i] = dt[i];
         c.dh[i] = dh[i];
+    }
+    if (T <= 0 || hout <= 0) {  // no rows: the sums are empty (a zero-block launch is an error)
+        hipError_t e = noff ? hipMemsetAsync(dW, 0, (size_t)noff * fout * 4, kf_stream()) : hipSuccess;
+        if (e == hipSuccess && db) e = hipMemsetAsync(db, 0, (size_t)fout * 4, kf_stream());
+        if (e != hipSuccess) {
+            lay_set_error("conv_c1_wgrad: %s", hipGetErrorString(e));
+            return -1;
+        }
+        return 0;
     }
     const long long rows = (long long)T * hout;
     // one round of workgroups, three per CU (rocprof, T = 96,000: 181 us at 768 against
@@ -431,9 +445,16 @@ __global__ __launch_bounds__(256) void k_rows_sum_list(h16 *edge, const h16 *src
     edge[c] = f2h(s);
 }
 
+// the lowest tail row (T-1) - 3(tc-tc0-1) must be a row of the source (the tail rows may
+// interleave with the head rows: the network's do)
+static bool tail_below_zero(int T, int tc0, int tc) {
+    return tc > tc0 && (long long)(T - 1) - 3LL * ((long long)tc - tc0 - 1) < 0;
+}
+
 int kf_gather_rows(void *dst, const void *src, long long row_bytes, int T, int tc0, int tc) {
     kf_take_pending(__func__);
-    if (row_bytes <= 0 || row_bytes % 16 || tc0 < 0 || tc < tc0 || T <= 0 || 3LL * (tc0 - 1) > T - 1) {
+    if (row_bytes <= 0 || row_bytes % 16 || tc0 < 0 || tc < tc0 || T <= 0 || 3LL * (tc0 - 1) > T - 1 ||
+        tail_below_zero(T, tc0, tc)) {
         lay_set_error("gather_rows: bad geometry (row_bytes %lld T %d tc0 %d tc %d)", row_bytes, T, tc0, tc);
         return -1;
     }
@@ -446,7 +467,7 @@ int kf_gather_rows(void *dst, const void *src, long long row_bytes, int T, int t
 int kf_scatter_rows_from(void *dst, const void *src, long long row_bytes, int T, int tc0, int tc, int r0) {
     kf_take_pending(__func__);
     if (row_bytes <= 0 || row_bytes % 16 || tc0 < 0 || tc < tc0 || T <= 0 || 3LL * (tc0 - 1) > T - 1 || r0 < 0 ||
-        r0 >= T) {
+        r0 >= T || tail_below_zero(T, tc0, tc)) {
         lay_set_error("scatter_rows: bad geometry (row_bytes %lld T %d tc0 %d tc %d r0 %d)", row_bytes, T, tc0, tc, r0);
         return -1;
     }

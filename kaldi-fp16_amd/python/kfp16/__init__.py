@@ -185,8 +185,8 @@ def _err(lib_fn):
 
 def check(rc, what="kfp16"):
     if rc != 0:
-        msgs = [m for m in (core.kf_last_error(), core.ops_last_error(), core.bridge_last_error(),
-                            nnet.nnet_last_error()) if m]
+        msgs = [m for m in (core.kf_last_error(), core.kf_layers_last_error(), core.ops_last_error(),
+                            core.bridge_last_error(), nnet.nnet_last_error()) if m]
         stale = core.kf_pending_log()
         if stale:   # errors other HIP calls left pending, consumed by the library's entry checks
             msgs.append(b"[" + stale + b"]")
@@ -565,3 +565,22 @@ _sig(core, "kf_gemm_wgrad_scaled", _i, _i, _i, _i, C.POINTER(KfOperand), C.POINT
 _sig(core, "kf_gemm_debug_kil", None, _i)
 _sig(core, "kf_gemm_trace", None, _vp, _i, _i)
 _sig(core, "kf_quant_mxfp8", _i, _vp, _ll, _i, _i, _i, _vp, _ll, _vp, _ll)
+# non-MFMA layer pieces (csrc/layers.hip) and the ivector input path (csrc/ivector.hip)
+_ip = C.POINTER(_i)
+_sig(core, "kf_small_gemm", _i, _vp, _i, _vp, _vp, _i, _i, _i, _i)
+_sig(core, "kf_bn_apply", _i, _vp, _vp, _ll, _i, _vp, _vp)
+_sig(core, "kf_conv_c1_forward", _i, _i, _i, _i, _i, _i, _i, _ip, _ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig(core, "kf_conv_c1_wgrad", _i, _i, _i, _i, _i, _i, _i, _ip, _ip, _vp, _vp, _vp, _vp)
+_sig(core, "kf_sgd_flat", _i, _vp, _vp, _vp, _vp, _f, _f, _ll)
+_sig(core, "kf_f32_to_f16_flat", _i, _vp, _vp, _ll)
+_sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)
+_sig(core, "kf_scatter_rows", _i, _vp, _vp, _ll, _i, _i, _i)
+_sig(core, "kf_scatter_rows_from", _i, _vp, _vp, _ll, _i, _i, _i, _i)
+_sig(core, "kf_rows_sum_list", _i, _vp, _vp, _ll, _ip, _i, _i)
+_sig(core, "kf_layers_last_error", C.c_char_p)
+_sig(core, "kf_combine_feature_maps", _i, _vp, _ll, _vp, _ll, _vp, _i, _vp, _ll, _i, _i, _i, _i)
+_sig(core, "kf_combine_feature_maps_backward", _i, _vp, _ll, _vp, _i, _vp, _ll, _i, _i, _i)
+_sig(core, "kf_im2col_small", _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _ip, _ip, _vp, _i)
+_sig(core, "kf_col2im_small", _i, _vp, _i, _i, _i, _i, _i, _i, _ip, _ip, _i, _vp, _ll)
+_sig(core, "kf_rows_gemm", _i, _vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i)
+_sig(core, "kf_rows_wgrad", _i, _vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i)
