@@ -89,6 +89,13 @@ typedef struct {
  * error and leaves the network unchanged. */
 int nnet_load_kaldi(KfNet *net, const KfNnet3Model *m, int mode, KfLoadStats *stats);
 
+/* Sets every update component's max-change and l2-regularize (kf_nnet.h
+ * nnet_set_component_opts) from the model's component of the same name (<MaxChange>,
+ * <L2Regularize>); the learning-rate factor stays as it is: learning rates are not taken
+ * from a model. A component the model lacks is an error and changes nothing. Works on a
+ * layout-only net. */
+int nnet_update_opts_from_kaldi(KfNet *net, const KfNnet3Model *m);
+
 #ifdef __cplusplus
 }
 #endif

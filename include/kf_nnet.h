@@ -93,6 +93,41 @@ void *nnet_weight_buffer(KfNet *net);
  * copies at the next forward, MXFP8 copies now) */
 int nnet_weights_changed(KfNet *net);
 int nnet_sgd(KfNet *net, float lr, float momentum);
+
+/* Kaldi-style parameter update (kf_ops.h kf_update_maxchange): momentum SGD
+ * with a per-component max-change, L2 term and learning-rate factor, and a global limit on
+ * the parameter change of one step.
+ * The trainable tensors are grouped into components, one per Kaldi nnet3 component, under
+ * the names nnet_load_kaldi reads: conv-relu-batchnorm <layer>.conv {W, Bias}; tdnnf
+ * <layer>.linear {LinearW} and <layer>.affine {AffineW, AffineBias}; linear-component
+ * <layer> {W}; prefinal prefinal-chain.affine | prefinal-xent.affine {BigW, BigBias} and
+ * .linear {SmallW}; output and attention <layer>.affine {W, Bias}. A component's tensors are
+ * consecutive: nnet_param_info(first_tensor .. first_tensor + num_tensors - 1); its segments
+ * of the flat buffer are each tensor's rows * cols elements (the alignment padding between
+ * tensors belongs to no component and is never touched).
+ * Options come from the xconfig keys max-change (default 0.75, output layers 1.5; 0 = no
+ * limit), l2-regularize (0) and learning-rate-factor (1) of the layer, which apply to both
+ * components of a two-component layer; nnet_set_component_opts overrides them.
+ * nnet_num_components, nnet_component_info and nnet_set_component_opts work on a
+ * layout-only net. Any out pointer may be NULL. */
+int nnet_num_components(const KfNet *net);
+int nnet_component_info(const KfNet *net, int idx, char *name, int namelen, float *max_change, float *l2,
+                        float *lr_factor, int *first_tensor, int *num_tensors);
+/* max_change >= 0, l2 >= 0, lr_factor > 0; an unknown name or a bad value is an error */
+int nnet_set_component_opts(KfNet *net, const char *name, float max_change, float l2, float lr_factor);
+/* One update of the master / fp16 / velocity buffers from the gradient buffer (as nnet_sgd:
+ * after nnet_backward, also a data-parallel one), asynchronous on the current stream.
+ * max_param_change >= 0 (0 = no limit; Kaldi's default is 2.0); l2_scale is Kaldi's factor on
+ * the L2 term, normally the minibatch's supervised frame count. The component tables and the
+ * scratch are uploaded / allocated at the first call and again after
+ * nnet_set_component_opts; nothing is allocated per step. Refreshes the derived weight
+ * copies as nnet_sgd does. */
+int nnet_update(KfNet *net, float lr, float momentum, float max_param_change, float l2_scale);
+/* Kaldi's per-component max-change report of the last nnet_update (synchronises): the
+ * step's norm n_c and scale s_c of components 0 .. n-1 (n <= nnet_num_components), the
+ * global norm N and scale S. */
+int nnet_update_stats(KfNet *net, float *norms, float *scales, int n, float *global_norm, float *global_scale);
+
 /* MXFP8 train step (BASELINE configs[4]): 1 = every TDNN-F / linear / prefinal / output
  * GEMM whose input has an MXFP8 copy runs on the fp8 MFMA (kf_ops.h MXFP8 operands);
  * the producing epilogues write those copies, weights are re-quantised on every

@@ -231,6 +231,49 @@ int kf_conv_c1_wgrad(int T, int hin, int hout, int sub, int fout, int noff, cons
 int kf_sgd_flat(float *w32, void *w16, const float *g, float *v, float lr, float mom,
                 long long n);
 int kf_f32_to_f16_flat(const float *src, void *dst, long long n);
+
+/* ---- Kaldi-style parameter update (csrc/update.hip) ----
+ * Momentum SGD over a flat parameter set whose elements are grouped into components, with a
+ * per-component L2 term and learning-rate factor, each component's step limited to its
+ * max-change and the whole step to max_param_change. For element i of component c:
+ *   v_i = momentum * v_i + g_i + l2_scale * l2_c * w32_i        (stored to v)
+ *   d_i = lr * lr_factor_c * v_i
+ *   n_c = sqrt(sum_i d_i^2),  s_c = max_change_c / n_c if max_change_c > 0 and n_c > max_change_c, else 1
+ *   N   = sqrt(sum_c (s_c n_c)^2),  S = max_param_change / N if max_param_change > 0 and N > it, else 1
+ *   w32_i -= S * s_c * d_i;  w16_i = rne_fp16(w32_i as stored)
+ * A component is a set of segments [begin, end) of the buffer (elements); what no segment
+ * covers is neither read nor written. Both tables live in device memory:
+ *   segments  sorted by component (each component's segments are consecutive), disjoint,
+ *             inside [0, n). A segment is cut into chunks of KF_UPD_CHUNK elements, one per
+ *             workgroup; first_wg = the number of chunks of all segments before it,
+ *             sum ceil((end - begin) / KF_UPD_CHUNK).
+ *   comps     first_wg = the first_wg of the component's first segment, num_wg = the chunks
+ *             of all its segments.
+ * Segments may begin and end anywhere; the body of a chunk moves 16-byte vectors and needs
+ * w32 / g / v 16-byte and w16 8-byte aligned bases. A table that breaks these rules gives
+ * wrong sums but addresses nothing outside [0, n).
+ * scratch: kf_update_scratch_bytes(n, nseg, ncomp) bytes of device memory, 8-byte aligned
+ * (-1: bad arguments): fp32 [n / KF_UPD_CHUNK + nseg] per-workgroup sums of d^2 (one launch
+ * slot per possible chunk), double [ncomp] (s_c n_c)^2, fp32 [ncomp] S * s_c * lr * lr_factor_c,
+ * each rounded up to 256 bytes; written and read within the call.
+ * stats: device fp32 [2 * ncomp + 2] = n_c [ncomp], s_c [ncomp], N, S of this call.
+ * Three launches on the current stream: no host synchronisation, allocation or atomics;
+ * every sum runs in a fixed order (the cross-workgroup ones in double), so the results are
+ * bit-identical from run to run. */
+#define KF_UPD_CHUNK 4096
+typedef struct KfUpdSegment {
+    long long begin, end;
+    int comp, first_wg;
+} KfUpdSegment;
+typedef struct KfUpdComp {
+    float max_change, l2, lr_factor; /* >= 0 (0: no limit), >= 0, > 0 */
+    int first_wg, num_wg;
+} KfUpdComp;
+long long kf_update_scratch_bytes(long long n, int nseg, int ncomp);
+int kf_update_maxchange(float *w32, void *w16, const float *g, float *v, long long n,
+                        const KfUpdSegment *segments, int nseg, const KfUpdComp *comps, int ncomp,
+                        float lr, float momentum, float max_param_change, float l2_scale,
+                        void *scratch, float *stats);
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.
  * Every source row must exist: 3(tc0-1) <= T-1 and, with a tail (tc > tc0), its lowest row

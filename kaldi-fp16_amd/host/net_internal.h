@@ -1,5 +1,5 @@
 // net_internal.h — the host layer's network state and the helpers its translation units
-// share: network.cpp (topology, allocation, parameters, fp8 set-up, sgd, data parallel),
+// share: network.cpp (topology, allocation, parameters, fp8 set-up, sgd / update, data parallel),
 // forward.cpp and backward.cpp. Nothing here is part of the C-ABI (kf_nnet.h).
 #pragma once
 #include <algorithm>
@@ -21,6 +21,14 @@ struct ParamRef {
     std::string name;
     int rows, cols;
     long long off;
+};
+
+// an update component (kf_nnet.h nnet_update): one Kaldi nnet3 component's tensors,
+// params[first .. first + count), and its options
+struct UpdComponent {
+    std::string name;
+    int first, count;
+    float max_change, l2, lr_factor;
 };
 
 // an MXFP8 tensor: e4m3 [rows x ld] + E8M0 scales [rows x ld/32] (kf_ops.h)
@@ -183,6 +191,14 @@ struct KfNet {
     Mx dz8[3];
     int dz8_layer[3] = {-1, -1, -1};
     bool wt_dirty = true;  // the transposed weight copies need a refresh (NetLayer::wt)
+    // nnet_update: the components, and their device tables (kf_ops.h KfUpdSegment / KfUpdComp),
+    // scratch and stats, made at the first update and again after an option changed
+    std::vector<UpdComponent> comps;
+    bool upd_dirty = true;
+    int upd_nseg = 0;
+    void *upd_segs = nullptr, *upd_comps = nullptr, *upd_scratch = nullptr;
+    float *upd_stats = nullptr;
+    bool upd_ran = false;  // upd_stats holds an update's report
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]

@@ -1,5 +1,6 @@
 // network.cpp — the network of the C++ host layer: topology, allocation, parameters and
-// setters, MXFP8 set-up, SGD, the data-parallel plan (forward.cpp / backward.cpp: the passes).
+// setters, MXFP8 set-up, SGD and the Kaldi-style update, the data-parallel plan (forward.cpp /
+// backward.cpp: the passes).
 //
 // Together they restate internal/nnet/forward.go (Network.Forward and the per-layer
 // forward functions), internal/nnet/network_backward.go (Network.Backward) and
@@ -346,6 +347,36 @@ static bool build_topology(KfNet *net, const char *xconfig_text, int max_frames,
             default:
                 set_err("layer " + n + ": type not supported on the MI355X path");
                 return false;
+        }
+        // the layer's update components (kf_nnet.h nnet_update): one per Kaldi nnet3 component,
+        // under the name nnet_load_kaldi reads it by, with the layer's options
+        auto comp = [&](const std::string &cname, int first, int count) {
+            net->comps.push_back(UpdComponent{cname, first, count, (float)L.max_change, (float)L.l2_regularize,
+                                              (float)L.lr_factor});
+        };
+        switch (L.type) {
+            case LayerType::ConvReluBN:
+                comp(n + ".conv", nl.pW, 2);
+                break;
+            case LayerType::TDNNF:
+                comp(n + ".linear", nl.pW, 1);
+                comp(n + ".affine", nl.pW2, 2);
+                break;
+            case LayerType::Linear:
+                comp(n, nl.pW, 1);
+                break;
+            case LayerType::Prefinal: {
+                const std::string pre = n.find("xent") != std::string::npos ? "prefinal-xent" : "prefinal-chain";
+                comp(pre + ".affine", nl.pW, 2);
+                comp(pre + ".linear", nl.pW2, 1);
+                break;
+            }
+            case LayerType::Output:
+            case LayerType::Attention:
+                comp(n + ".affine", nl.pW, 2);
+                break;
+            default:
+                break;
         }
         index[L.name] = (int)net->layers.size();
         net->layers.push_back(nl);
@@ -975,6 +1006,148 @@ extern "C" int nnet_sgd(KfNet *net, float lr, float momentum) {
     net->wt_dirty = true;
     // the MXFP8 weight copies follow every parameter change
     return net->fp8 && !quantise_weights(net, false) ? -1 : 0;
+}
+
+// ---------------------------------------------------------------------------
+// Kaldi-style update (kf_nnet.h nnet_update): per-component max-change, L2 and
+// learning-rate factor over the flat buffers, one kf_update_maxchange call per step
+// ---------------------------------------------------------------------------
+// The two kernels' entry points are weak references: a program that links the host layer
+// against a backend without them (the tests' launch-trace stub) still links, and
+// nnet_update reports them missing.
+#pragma weak kf_update_maxchange
+#pragma weak kf_update_scratch_bytes
+
+extern "C" int nnet_num_components(const KfNet *net) { return net ? (int)net->comps.size() : -1; }
+
+extern "C" int nnet_component_info(const KfNet *net, int idx, char *name, int namelen, float *max_change, float *l2,
+                                   float *lr_factor, int *first_tensor, int *num_tensors) {
+    if (!net || idx < 0 || idx >= (int)net->comps.size()) return -1;
+    const UpdComponent &c = net->comps[idx];
+    if (name && namelen > 0) snprintf(name, namelen, "%s", c.name.c_str());
+    if (max_change) *max_change = c.max_change;
+    if (l2) *l2 = c.l2;
+    if (lr_factor) *lr_factor = c.lr_factor;
+    if (first_tensor) *first_tensor = c.first;
+    if (num_tensors) *num_tensors = c.count;
+    return 0;
+}
+
+extern "C" int nnet_set_component_opts(KfNet *net, const char *name, float max_change, float l2, float lr_factor) {
+    if (!net || !name) {
+        set_err("set_component_opts: null argument");
+        return -1;
+    }
+    if (!(max_change >= 0) || !(l2 >= 0) || !(lr_factor > 0)) {
+        set_err(std::string("set_component_opts: ") + name + " needs max-change >= 0, l2-regularize >= 0 and "
+                "learning-rate-factor > 0, got " + std::to_string(max_change) + ", " + std::to_string(l2) + ", " +
+                std::to_string(lr_factor));
+        return -1;
+    }
+    for (UpdComponent &c : net->comps)
+        if (c.name == name) {
+            c.max_change = max_change;
+            c.l2 = l2;
+            c.lr_factor = lr_factor;
+            net->upd_dirty = true;
+            return 0;
+        }
+    set_err(std::string("set_component_opts: no component ") + name);
+    return -1;
+}
+
+// the device tables of the update: segments once, the components' options whenever they changed
+static bool upload_update_tables(KfNet *net) {
+    const int ncomp = (int)net->comps.size();
+    std::vector<KfUpdSegment> segs;
+    std::vector<KfUpdComp> comps(ncomp);
+    int wg = 0;
+    for (int c = 0; c < ncomp; ++c) {
+        const UpdComponent &u = net->comps[c];
+        comps[c] = KfUpdComp{u.max_change, u.l2, u.lr_factor, wg, 0};
+        for (int pi = u.first; pi < u.first + u.count; ++pi) {
+            const ParamRef &p = net->params[pi];
+            const long long len = (long long)p.rows * p.cols;
+            segs.push_back(KfUpdSegment{p.off, p.off + len, c, wg});
+            wg += (int)((len + KF_UPD_CHUNK - 1) / KF_UPD_CHUNK);
+        }
+        comps[c].num_wg = wg - comps[c].first_wg;
+    }
+    static_assert(sizeof(KfUpdSegment) % 4 == 0 && sizeof(KfUpdComp) % 4 == 0, "uploaded as 32-bit words");
+    if (!net->upd_segs) {
+        const long long sb = kf_update_scratch_bytes(net->nparams, (int)segs.size(), ncomp);
+        if (sb < 0) {
+            set_err("update: scratch size");
+            return false;
+        }
+        net->upd_nseg = (int)segs.size();
+        net->upd_segs = net->dalloc(segs.size() * sizeof(KfUpdSegment));
+        net->upd_comps = net->dalloc(comps.size() * sizeof(KfUpdComp));
+        net->upd_scratch = net->dalloc((size_t)sb);
+        net->upd_stats = (float *)net->dalloc((size_t)(2 * ncomp + 2) * 4);
+        if (!net->upd_segs || !net->upd_comps || !net->upd_scratch || !net->upd_stats ||
+            bridge_transfer_int32(net->upd_segs, (const int32_t *)segs.data(), segs.size() * sizeof(KfUpdSegment) / 4)) {
+            net->upd_segs = nullptr;  // (the buffers stay with the net's allocations until it is freed)
+            set_err("update: alloc / upload of the segment table");
+            return false;
+        }
+    }
+    if (bridge_transfer_int32(net->upd_comps, (const int32_t *)comps.data(), comps.size() * sizeof(KfUpdComp) / 4)) {
+        set_err("update: upload of the component table");
+        return false;
+    }
+    net->upd_dirty = false;
+    return true;
+}
+
+extern "C" int nnet_update(KfNet *net, float lr, float momentum, float max_param_change, float l2_scale) {
+    kf_take_pending(__func__);
+    if (!on_device(net, "update")) return -1;
+    if (!kf_update_maxchange || !kf_update_scratch_bytes) {
+        set_err("update: this build of libkaldi_fp16 has no kf_update_maxchange");
+        return -1;
+    }
+    if (!(max_param_change >= 0)) {
+        set_err("update: max_param_change must be >= 0");
+        return -1;
+    }
+    if (net->comps.empty()) return 0;
+    if (net->upd_dirty && !upload_update_tables(net)) return -1;
+    if (!ck(kf_update_maxchange(net->master, net->w16, net->grad, net->vel, net->nparams,
+                                (const KfUpdSegment *)net->upd_segs, net->upd_nseg, (const KfUpdComp *)net->upd_comps,
+                                (int)net->comps.size(), lr, momentum, max_param_change, l2_scale, net->upd_scratch,
+                                net->upd_stats),
+            "update"))
+        return -1;
+    net->upd_ran = true;
+    net->wt_dirty = true;
+    // the MXFP8 weight copies follow every parameter change
+    return net->fp8 && !quantise_weights(net, false) ? -1 : 0;
+}
+
+extern "C" int nnet_update_stats(KfNet *net, float *norms, float *scales, int n, float *global_norm,
+                                 float *global_scale) {
+    if (!on_device(net, "update_stats")) return -1;
+    const int ncomp = (int)net->comps.size();
+    if (!net->upd_ran || n < 0 || n > ncomp) {
+        set_err(net->upd_ran ? "update_stats: more components asked for than the network has"
+                             : "update_stats: no nnet_update has run");
+        return -1;
+    }
+    // D2H through the bridge, ordered behind the update on the current stream (fp32 read =
+    // 2x fp16 count, as nnet_get_params)
+    std::vector<float> st((size_t)2 * ncomp + 2);
+    if (bridge_read_fp16((uint16_t *)st.data(), net->upd_stats, st.size() * 2)) {
+        set_err("update_stats: read");
+        return -1;
+    }
+    for (int c = 0; c < n; ++c) {
+        if (norms) norms[c] = st[c];
+        if (scales) scales[c] = st[ncomp + c];
+    }
+    if (global_norm) *global_norm = st[2 * ncomp];
+    if (global_scale) *global_scale = st[2 * ncomp + 1];
+    return 0;
 }
 
 // Parse + resolve only (no device work): one line per layer

@@ -673,3 +673,43 @@ extern "C" int nnet_load_kaldi(KfNet *net, const KfNnet3Model *m, int mode, KfLo
     if (stats) *stats = L.st;
     return 0;
 }
+
+// <MaxChange> and <L2Regularize> of the model's components -> the update components of the
+// same names (kf_nnet.h nnet_set_component_opts). Every component is looked up before any
+// option is set; the learning-rate factor is kept.
+extern "C" int nnet_update_opts_from_kaldi(KfNet *net, const KfNnet3Model *m) {
+    if (!net || !m) {
+        set_err("nnet_update_opts_from_kaldi: bad arguments");
+        return -1;
+    }
+    struct Opt {
+        std::string name;
+        float maxc, l2, lrf;
+    };
+    std::vector<Opt> opts;
+    const int nc = nnet_num_components(net);
+    for (int i = 0; i < nc; ++i) {
+        char nm[256];
+        float lrf = 1.f;
+        if (nnet_component_info(net, i, nm, sizeof(nm), nullptr, nullptr, &lrf, nullptr, nullptr) != 0) {
+            set_err("nnet_component_info failed");
+            return -1;
+        }
+        const Comp *c = m->get(nm);
+        if (!c) {
+            set_err("%s not found", nm);
+            return -1;
+        }
+        if (!(c->maxc >= 0) || !(c->l2 >= 0)) {
+            set_err("%s: <MaxChange> %g and <L2Regularize> %g must be >= 0", nm, (double)c->maxc, (double)c->l2);
+            return -1;
+        }
+        opts.push_back(Opt{nm, c->maxc, c->l2, lrf});
+    }
+    for (const Opt &o : opts)
+        if (nnet_set_component_opts(net, o.name.c_str(), o.maxc, o.l2, o.lrf) != 0) {
+            set_err("nnet_set_component_opts: %s", nnet_last_error() ? nnet_last_error() : "failed");
+            return -1;
+        }
+    return 0;
+}

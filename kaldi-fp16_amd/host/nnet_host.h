@@ -60,6 +60,8 @@ struct Layer {  // layers.go:12-120 (specs flattened)
     // attention-relu-batchnorm (layers.go:298-321, AttentionSpec :92-104)
     int num_heads = 1, key_dim = 0, value_dim = 0, num_left = 0, num_right = 0, att_stride = 1;
     double key_scale = 0;  // 0 -> 1/sqrt(key_dim) (weight_loader.go:266-271)
+    // update options of the layer's components (Kaldi's xconfig defaults; kf_nnet.h nnet_update)
+    double max_change = 0.75, l2_regularize = 0, lr_factor = 1;
 };
 
 bool ParseXConfig(const std::string &text, std::vector<LayerConfig> &out, std::string &err);

@@ -298,6 +298,14 @@ bool ResolveLayers(const std::vector<LayerConfig> &cfgs, std::vector<Layer> &lay
                 break;
             }
         }
+        // max-change / l2-regularize / learning-rate-factor of the layer's components
+        // (Kaldi's xconfig defaults: 0.75, 1.5 on an output layer; 0; 1)
+        L.max_change = cfg.get_float("max-change", cfg.type == LayerType::Output ? 1.5 : 0.75);
+        L.l2_regularize = cfg.get_float("l2-regularize", 0.0);
+        L.lr_factor = cfg.get_float("learning-rate-factor", 1.0);
+        if (!(L.max_change >= 0)) return fail("max-change must be >= 0, got " + cfg.get("max-change", ""));
+        if (!(L.l2_regularize >= 0)) return fail("l2-regularize must be >= 0, got " + cfg.get("l2-regularize", ""));
+        if (!(L.lr_factor > 0)) return fail("learning-rate-factor must be > 0, got " + cfg.get("learning-rate-factor", ""));
         layers.push_back(L);
     }
     return true;

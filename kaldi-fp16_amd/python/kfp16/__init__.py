@@ -140,6 +140,12 @@ _sig(nnet, "nnet_master_buffer", _vp, _vp)
 _sig(nnet, "nnet_weight_buffer", _vp, _vp)
 _sig(nnet, "nnet_sgd", _i, _vp, _f, _f)
 _sig(nnet, "nnet_set_fp8", _i, _vp, _i)
+_fp = C.POINTER(_f)
+_sig(nnet, "nnet_num_components", _i, _vp)
+_sig(nnet, "nnet_component_info", _i, _vp, _i, C.c_char_p, _i, _fp, _fp, _fp, C.POINTER(_i), C.POINTER(_i))
+_sig(nnet, "nnet_set_component_opts", _i, _vp, C.c_char_p, _f, _f, _f)
+_sig(nnet, "nnet_update", _i, _vp, _f, _f, _f, _f)
+_sig(nnet, "nnet_update_stats", _i, _vp, _vp, _vp, _i, _fp, _fp)
 _sig(nnet, "nnet_bind_grad_buffer", _i, _vp, _vp)
 _sig(nnet, "nnet_backward_n", _i, _vp, _vp, _i)
 _sig(nnet, "nnet_debug_tensor", _vp, _vp, C.c_char_p, _i)
@@ -423,6 +429,43 @@ class Network:
     def sgd(self, lr: float, momentum: float):
         check(nnet.nnet_sgd(self.h, float(lr), float(momentum)), "nnet_sgd")
 
+    # Kaldi-style update (kf_nnet.h nnet_update) ----------------------------
+    def components(self) -> list:
+        """The update components, one per Kaldi nnet3 component: dicts of name, max_change,
+        l2, lr_factor and tensors (the names of its parameter tensors, in layout order)."""
+        names = list(self.params)
+        name = C.create_string_buffer(256)
+        mc, l2, lrf, first, cnt = _f(), _f(), _f(), _i(), _i()
+        out = []
+        for i in range(nnet.nnet_num_components(self.h)):
+            check(nnet.nnet_component_info(self.h, i, name, 256, C.byref(mc), C.byref(l2), C.byref(lrf),
+                                           C.byref(first), C.byref(cnt)), "nnet_component_info")
+            out.append(dict(name=name.value.decode(), max_change=mc.value, l2=l2.value, lr_factor=lrf.value,
+                            tensors=names[first.value:first.value + cnt.value]))
+        return out
+
+    def set_component_opts(self, name: str, max_change: float, l2: float = 0.0, lr_factor: float = 1.0):
+        """Override a component's max-change (0: no limit), l2-regularize and learning-rate-factor."""
+        check(nnet.nnet_set_component_opts(self.h, name.encode(), float(max_change), float(l2), float(lr_factor)),
+              "nnet_set_component_opts")
+
+    def update(self, lr: float, momentum: float, max_param_change: float = 2.0, l2_scale: float = 1.0):
+        """One Kaldi-style update: momentum SGD with per-component max-change, L2 and
+        learning-rate factors and the global max_param_change (0: no limit). l2_scale: Kaldi's
+        factor on the L2 term, normally the minibatch's supervised frame count."""
+        check(nnet.nnet_update(self.h, float(lr), float(momentum), float(max_param_change), float(l2_scale)),
+              "nnet_update")
+
+    def update_stats(self) -> dict:
+        """The last update's max-change report (synchronises): norms n_c and scales s_c per
+        component (in components() order), global_norm N and global_scale S."""
+        n = nnet.nnet_num_components(self.h)
+        norms, scales = np.empty(n, np.float32), np.empty(n, np.float32)
+        gn, gs = _f(), _f()
+        check(nnet.nnet_update_stats(self.h, norms.ctypes.data, scales.ctypes.data, n, C.byref(gn), C.byref(gs)),
+              "nnet_update_stats")
+        return dict(norms=norms, scales=scales, global_norm=gn.value, global_scale=gs.value)
+
     def dp_plan(self, bucket_bytes: int, max_buckets: int = 256):
         """[(after_step, begin, end)]: the gradient buckets nnet_backward exchanges
         (kf_nnet.h nnet_dp_plan), in issue order."""
@@ -573,6 +616,19 @@ _sig(core, "kf_conv_c1_forward", _i, _i, _i, _i, _i, _i, _i, _ip, _ip, _vp, _vp,
 _sig(core, "kf_conv_c1_wgrad", _i, _i, _i, _i, _i, _i, _i, _ip, _ip, _vp, _vp, _vp, _vp)
 _sig(core, "kf_sgd_flat", _i, _vp, _vp, _vp, _vp, _f, _f, _ll)
 _sig(core, "kf_f32_to_f16_flat", _i, _vp, _vp, _ll)
+
+
+class KfUpdSegment(C.Structure):
+    _fields_ = [("begin", _ll), ("end", _ll), ("comp", _i), ("first_wg", _i)]
+
+
+class KfUpdComp(C.Structure):
+    _fields_ = [("max_change", _f), ("l2", _f), ("lr_factor", _f), ("first_wg", _i), ("num_wg", _i)]
+
+
+UPD_CHUNK = 4096  # kf_ops.h KF_UPD_CHUNK
+_sig(core, "kf_update_scratch_bytes", _ll, _ll, _i, _i)
+_sig(core, "kf_update_maxchange", _i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp, _vp)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows_from", _i, _vp, _vp, _ll, _i, _i, _i, _i)

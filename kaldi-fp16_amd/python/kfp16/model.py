@@ -46,6 +46,7 @@ _sig("kf_nnet3_component", _i, _vp, _i, C.POINTER(KfNnet3Component))
 _sig("kf_nnet3_find", _i, _vp, C.c_char_p)
 _sig("nnet_load_kaldi", _i, _vp, _vp, _i, C.POINTER(KfLoadStats))
 _sig("nnet_set_idct", _i, _vp, C.c_char_p, _vp, _i, _i)
+_sig("nnet_update_opts_from_kaldi", _i, _vp, _vp)
 
 
 class ModelError(KfError):
@@ -144,6 +145,12 @@ class Nnet3Model:
         if nnet.nnet_load_kaldi(net.h, self._h, mode, C.byref(st)) != 0:
             raise ModelError(last_error())
         return st
+
+    def update_opts_into(self, net) -> None:
+        """Each update component's max-change and l2-regularize from the model's component of
+        the same name (kf_model.h nnet_update_opts_from_kaldi); learning rates are not taken."""
+        if nnet.nnet_update_opts_from_kaldi(net.h, self._h) != 0:
+            raise ModelError(last_error())
 
     def close(self):
         if self._h:

@@ -7,7 +7,9 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
      (chain_loss.go:221-294)         frame_offset + left_context + k * subsampling for
                                      k < frames_per_seq, cut where the eg ends
   3. Backward                     -> Network.backward (seeded at the chain output)
-  4. optimizer.Update per tensor  -> Network.sgd over the flat buffer (optimize.go:95-142)
+  4. optimizer.Update per tensor  -> Network.sgd over the flat buffer (optimize.go:95-142),
+                                     or with TrainConfig.kaldi_update Network.update: Kaldi's
+                                     per-component max-change, L2 and learning-rate factors
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
 
 The numerator FSTs come from the batch's per-sequence CSRs (TrainingBatch.PerSeqCSRs),
@@ -37,6 +39,13 @@ class TrainConfig:
     subsampling_factor: int = 3
     left_context: int = 30
     opts: _chain.KfChainOpts | None = None
+    # kaldi_update: step 4 is Network.update (per-component max-change / l2-regularize /
+    # learning-rate-factor from the xconfig or Network.set_component_opts) with the global
+    # max_param_change (0: no limit; Kaldi's recipes use 2.0) and l2_scale (None: the batch's
+    # supervised frame count, Kaldi's factor). False: the plain Network.sgd, as before.
+    kaldi_update: bool = False
+    max_param_change: float = 0.0
+    l2_scale: float | None = None
 
 
 def chain_rows(frame_offsets, num_frames, frames_per_seq, subsampling: int, left_context: int):
@@ -105,7 +114,11 @@ class EgsTrainer:
         self.net.backward(self.grad_out.ptr)
         if allreduce is not None:
             allreduce()
-        self.net.sgd(self.cfg.learning_rate, self.cfg.momentum)
+        if self.cfg.kaldi_update:
+            l2_scale = float(frames.sum()) if self.cfg.l2_scale is None else self.cfg.l2_scale
+            self.net.update(self.cfg.learning_rate, self.cfg.momentum, self.cfg.max_param_change, l2_scale)
+        else:
+            self.net.sgd(self.cfg.learning_rate, self.cfg.momentum)
 
     def result(self):
         sync()
