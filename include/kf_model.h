@@ -64,6 +64,9 @@ void kf_nnet3_free(KfNnet3Model *m);
 int kf_nnet3_num_components(const KfNnet3Model *m);
 /* components in first-appearance order */
 int kf_nnet3_component(const KfNnet3Model *m, int idx, KfNnet3Component *out);
+/* <OrthonormalConstraint> of a TdnnComponent / LinearComponent line: 1 and the value when
+ * the line has the tag, 0 (and *c = 0) when it has not, -1 on a bad index */
+int kf_nnet3_component_orthonormal(const KfNnet3Model *m, int idx, float *c);
 /* index of a component by name, -1 if absent */
 int kf_nnet3_find(const KfNnet3Model *m, const char *name);
 
@@ -93,7 +96,10 @@ int nnet_load_kaldi(KfNet *net, const KfNnet3Model *m, int mode, KfLoadStats *st
  * nnet_set_component_opts) from the model's component of the same name (<MaxChange>,
  * <L2Regularize>); the learning-rate factor stays as it is: learning rates are not taken
  * from a model. A component the model lacks is an error and changes nothing. Works on a
- * layout-only net. */
+ * layout-only net.
+ * The orthonormal constraint (kf_nnet.h nnet_set_component_orthonormal) is carried over only
+ * where the model's line has an <OrthonormalConstraint> tag; without the tag the net's value
+ * stays. A non-zero value on a component that cannot take it is an error and changes nothing. */
 int nnet_update_opts_from_kaldi(KfNet *net, const KfNnet3Model *m);
 
 #ifdef __cplusplus

@@ -128,6 +128,37 @@ int nnet_update(KfNet *net, float lr, float momentum, float max_param_change, fl
  * global norm N and scale S. */
 int nnet_update_stats(KfNet *net, float *norms, float *scales, int n, float *global_norm, float *global_scale);
 
+/* Semi-orthogonal constraint (kf_ops.h kf_orthonormal_constrain): Kaldi's
+ * ConstrainOrthonormal, which keeps a TDNN-F bottleneck matrix and the prefinal layers' small
+ * projection close to semi-orthogonal. Every update component whose tensor is one weight
+ * matrix W [K x n] carries a constraint value c: 0 off, > 0 a fixed scale, < 0 the floating
+ * scale. It comes from the xconfig key orthonormal-constraint: default -1 on a tdnnf-layer
+ * (its <layer>.linear, never .affine) and a prefinal-layer (its .linear, SmallW), 0 on a
+ * linear-component; every other component is at 0. The first three entry points work on a
+ * layout-only net. */
+int nnet_component_orthonormal(const KfNet *net, int idx, float *c);
+/* An unknown name, a component that is not a single weight matrix, a non-finite c, or a
+ * c != 0 on a shape the kernel does not take (it needs K and n multiples of 32,
+ * 32 <= n <= K, n <= 512; n > K is Kaldi's transposed case, not supported) is an error. */
+int nnet_set_component_orthonormal(KfNet *net, const char *name, float c);
+/* The constrained components (c != 0), in nnet_component_info order: returns their number
+ * and writes the component indices of the first n to idx (may be NULL). */
+int nnet_orthonormal_components(const KfNet *net, int *idx, int n);
+/* One application of the constraint to every constrained component's fp32 master matrix and
+ * its fp16 copy (the velocity is not touched), asynchronous on the current stream. Kaldi
+ * skips each component at random with probability 3/4; here every constrained component is
+ * handled at every call and the schedule is the caller's (every fourth step gives Kaldi's
+ * rate). The matrix table and the scratch are uploaded / allocated at the first call and again
+ * after nnet_set_component_orthonormal; nothing is allocated per call. Refreshes the derived
+ * weight copies as nnet_sgd does. A net without a constrained component returns 0 and
+ * launches nothing. */
+int nnet_constrain_orthonormal(KfNet *net);
+/* The report of the last nnet_constrain_orthonormal (synchronises), measured before that
+ * call's update: scale s, ratio (1 with a fixed scale) and err = |W^T W - s^2 I|_F of the
+ * first n constrained components (n <= nnet_orthonormal_components; s = 0: the matrix was
+ * all-zero or not finite and was left untouched). Any out pointer may be NULL. */
+int nnet_orthonormal_stats(KfNet *net, float *scale, float *ratio, float *err, int n);
+
 /* MXFP8 train step (BASELINE configs[4]): 1 = every TDNN-F / linear / prefinal / output
  * GEMM whose input has an MXFP8 copy runs on the fp8 MFMA (kf_ops.h MXFP8 operands);
  * the producing epilogues write those copies, weights are re-quantised on every

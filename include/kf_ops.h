@@ -274,6 +274,43 @@ int kf_update_maxchange(float *w32, void *w16, const float *g, float *v, long lo
                         const KfUpdSegment *segments, int nseg, const KfUpdComp *comps, int ncomp,
                         float lr, float momentum, float max_param_change, float l2_scale,
                         void *scratch, float *stats);
+
+/* ---- Semi-orthogonal constraint (csrc/orthonormal.hip) ----
+ * Kaldi's ConstrainOrthonormal over every constrained matrix of a flat parameter set in one
+ * call. A matrix is W [K rows x n cols] (y = x W, the transpose of Kaldi's M: the columns
+ * are constrained) at elements [offset, offset + K n) of w32 / w16, with a constraint value
+ * c: 0 off, > 0 a fixed scale, < 0 the floating scale. On the fp32 weights:
+ *   P = W^T W (fp32, exact f32-input MFMA),  nu = 0.125
+ *   c < 0:  tP = tr P, tPP = sum P_ij^2 (double), s = sqrt(tPP / tP), ratio = tPP n / tP^2,
+ *           nu *= 0.5 if ratio > 1.02, and again if ratio > 1.1
+ *   c > 0:  s = c, ratio = 1
+ *   Q = P - s^2 I,  err = sqrt(sum Q_ij^2)
+ *   w32 -= 4 (nu / s^2) W Q;  w16 = rne_fp16(w32 as stored)
+ * A matrix with tP == 0 or a non-finite s is left untouched and reports s = 0 (and ratio,
+ * err, nu 0). Supported shapes: K % 32 == 0, n % 32 == 0, 32 <= n <= K, n <= 512; any other
+ * shape with c != 0, a non-finite c or a matrix outside [0, n_params) returns -1 before
+ * anything is launched. Matrices must not overlap; what no matrix covers is neither read nor
+ * written, nor is a matrix with c == 0.
+ * mats is the table in host memory (checked, sizes the launches), mats_dev the same table in
+ * device memory (read by the kernels), uploaded once by the caller.
+ * scratch: kf_orthonormal_scratch_bytes(mats, nmat) bytes of device memory, 16-byte aligned
+ * (-1: a bad table): fp32 [nmat] factors 4 nu / s^2 rounded up to 256 bytes, then per
+ * constrained matrix ceil(K / KF_ORTHO_KCHUNK) partial n x n tiles of P and the n x n Q;
+ * written and read within the call.
+ * stats: device fp32 [4 * nmat] = s, ratio, err, nu per matrix (zeros where c == 0).
+ * Three launches on the current stream whatever nmat is (none when no c != 0): no host
+ * synchronisation, allocation or atomics; every sum runs in a fixed order, so the results
+ * are bit-identical from run to run. */
+#define KF_ORTHO_KCHUNK 512
+typedef struct KfOrthoMat {
+    long long offset;
+    int K, n;
+    float c;
+    int reserved; /* 0 */
+} KfOrthoMat;
+long long kf_orthonormal_scratch_bytes(const KfOrthoMat *mats, int nmat);
+int kf_orthonormal_constrain(float *w32, void *w16, long long n_params, const KfOrthoMat *mats,
+                             const KfOrthoMat *mats_dev, int nmat, void *scratch, float *stats);
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.
  * Every source row must exist: 3(tc0-1) <= T-1 and, with a tail (tc > tc0), its lowest row

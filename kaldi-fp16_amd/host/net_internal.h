@@ -29,6 +29,7 @@ struct UpdComponent {
     std::string name;
     int first, count;
     float max_change, l2, lr_factor;
+    float orthonormal;  // kf_nnet.h nnet_constrain_orthonormal: 0 off, > 0 fixed scale, < 0 floating
 };
 
 // an MXFP8 tensor: e4m3 [rows x ld] + E8M0 scales [rows x ld/32] (kf_ops.h)
@@ -199,6 +200,17 @@ struct KfNet {
     void *upd_segs = nullptr, *upd_comps = nullptr, *upd_scratch = nullptr;
     float *upd_stats = nullptr;
     bool upd_ran = false;  // upd_stats holds an update's report
+    // nnet_constrain_orthonormal: the constrained components (indices into comps, in comps'
+    // order), their matrix table on the host and on the device (kf_ops.h KfOrthoMat), scratch
+    // and stats, made at the first call and again after nnet_set_component_orthonormal
+    bool ort_dirty = true;
+    std::vector<int> ort_comps;
+    std::vector<KfOrthoMat> ort_mats;
+    void *ort_mats_dev = nullptr, *ort_scratch = nullptr;
+    float *ort_stats = nullptr;
+    size_t ort_cap = 0;         // entries ort_mats_dev / ort_stats hold
+    long long ort_scratch_bytes = 0;
+    bool ort_ran = false;  // ort_stats holds a call's report
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]

@@ -352,23 +352,28 @@ static bool build_topology(KfNet *net, const char *xconfig_text, int max_frames,
         // under the name nnet_load_kaldi reads it by, with the layer's options
         auto comp = [&](const std::string &cname, int first, int count) {
             net->comps.push_back(UpdComponent{cname, first, count, (float)L.max_change, (float)L.l2_regularize,
-                                              (float)L.lr_factor});
+                                              (float)L.lr_factor, 0.f});
+        };
+        // the one weight matrix the layer's orthonormal-constraint applies to
+        auto comp_orth = [&](const std::string &cname, int first) {
+            comp(cname, first, 1);
+            net->comps.back().orthonormal = (float)L.orthonormal;
         };
         switch (L.type) {
             case LayerType::ConvReluBN:
                 comp(n + ".conv", nl.pW, 2);
                 break;
             case LayerType::TDNNF:
-                comp(n + ".linear", nl.pW, 1);
+                comp_orth(n + ".linear", nl.pW);
                 comp(n + ".affine", nl.pW2, 2);
                 break;
             case LayerType::Linear:
-                comp(n, nl.pW, 1);
+                comp_orth(n, nl.pW);
                 break;
             case LayerType::Prefinal: {
                 const std::string pre = n.find("xent") != std::string::npos ? "prefinal-xent" : "prefinal-chain";
                 comp(pre + ".affine", nl.pW, 2);
-                comp(pre + ".linear", nl.pW2, 1);
+                comp_orth(pre + ".linear", nl.pW2);
                 break;
             }
             case LayerType::Output:
@@ -1147,6 +1152,160 @@ extern "C" int nnet_update_stats(KfNet *net, float *norms, float *scales, int n,
     }
     if (global_norm) *global_norm = st[2 * ncomp];
     if (global_scale) *global_scale = st[2 * ncomp + 1];
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Semi-orthogonal constraint (kf_nnet.h nnet_constrain_orthonormal): Kaldi's
+// ConstrainOrthonormal over every constrained component, one kf_orthonormal_constrain call
+// ---------------------------------------------------------------------------
+// weak, as the update's entry points above: the launch-trace stub backend has neither
+#pragma weak kf_orthonormal_constrain
+#pragma weak kf_orthonormal_scratch_bytes
+
+extern "C" int nnet_component_orthonormal(const KfNet *net, int idx, float *c) {
+    if (!net || idx < 0 || idx >= (int)net->comps.size()) return -1;
+    if (c) *c = net->comps[idx].orthonormal;
+    return 0;
+}
+
+// the shapes csrc/orthonormal.hip takes (kf_ops.h): W [K x n], columns constrained
+static bool ortho_shape_ok(int K, int n) { return n >= 32 && K % 32 == 0 && n % 32 == 0 && n <= K && n <= 512; }
+
+extern "C" int nnet_set_component_orthonormal(KfNet *net, const char *name, float c) {
+    if (!net || !name) {
+        set_err("set_component_orthonormal: null argument");
+        return -1;
+    }
+    if (!std::isfinite(c)) {
+        set_err(std::string("set_component_orthonormal: ") + name + " needs a finite value");
+        return -1;
+    }
+    for (UpdComponent &u : net->comps) {
+        if (u.name != name) continue;
+        const ParamRef &p = net->params[u.first];
+        if (u.count != 1 || p.rows <= 1) {
+            set_err(std::string("set_component_orthonormal: ") + name + " is not a single weight matrix");
+            return -1;
+        }
+        if (c != 0.f && !ortho_shape_ok(p.rows, p.cols)) {
+            const std::string shape = std::to_string(p.rows) + " x " + std::to_string(p.cols);
+            set_err(std::string("set_component_orthonormal: ") + name + " is " + shape +
+                    (p.cols > p.rows ? " (n > K): transposed case not supported"
+                                     : ": needs K and n multiples of 32, 32 <= n <= K, n <= 512 (the transposed case "
+                                       "not supported either)"));
+            return -1;
+        }
+        u.orthonormal = c;
+        net->ort_dirty = true;
+        return 0;
+    }
+    set_err(std::string("set_component_orthonormal: no component ") + name);
+    return -1;
+}
+
+// the constrained components (c != 0), in nnet_component_info order
+static void ortho_list(const KfNet *net, std::vector<int> &idx) {
+    idx.clear();
+    for (size_t i = 0; i < net->comps.size(); ++i)
+        if (net->comps[i].orthonormal != 0.f) idx.push_back((int)i);
+}
+
+extern "C" int nnet_orthonormal_components(const KfNet *net, int *idx, int n) {
+    if (!net || n < 0) return -1;
+    std::vector<int> v;
+    ortho_list(net, v);
+    for (int i = 0; i < n && i < (int)v.size(); ++i)
+        if (idx) idx[i] = v[i];
+    return (int)v.size();
+}
+
+// the matrix table, scratch and stats of the constraint: made when the set of constrained
+// components or a value changed; device buffers only grow
+static bool upload_ortho_table(KfNet *net) {
+    ortho_list(net, net->ort_comps);
+    net->ort_mats.clear();
+    for (int ci : net->ort_comps) {
+        const UpdComponent &u = net->comps[ci];
+        const ParamRef &p = net->params[u.first];
+        if (u.count != 1 || !ortho_shape_ok(p.rows, p.cols)) {
+            set_err("constrain_orthonormal: " + u.name + " is " + std::to_string(p.rows) + " x " + std::to_string(p.cols) +
+                    ": a constrained matrix needs K and n multiples of 32, 32 <= n <= K, n <= 512 (transposed case "
+                    "not supported); set its orthonormal-constraint to 0");
+            return false;
+        }
+        net->ort_mats.push_back(KfOrthoMat{p.off, p.rows, p.cols, u.orthonormal, 0});
+    }
+    net->ort_ran = false;
+    const size_t nm = net->ort_mats.size();
+    if (nm == 0) {
+        net->ort_dirty = false;
+        return true;
+    }
+    const long long sb = kf_orthonormal_scratch_bytes(net->ort_mats.data(), (int)nm);
+    if (sb < 0) {
+        set_err("constrain_orthonormal: scratch size");
+        return false;
+    }
+    static_assert(sizeof(KfOrthoMat) % 4 == 0, "uploaded as 32-bit words");
+    if (nm > net->ort_cap) {
+        net->ort_mats_dev = net->dalloc(nm * sizeof(KfOrthoMat));
+        net->ort_stats = (float *)net->dalloc(nm * 4 * sizeof(float));
+        net->ort_cap = net->ort_mats_dev && net->ort_stats ? nm : 0;
+    }
+    if (sb > net->ort_scratch_bytes) {
+        net->ort_scratch = net->dalloc((size_t)sb);
+        net->ort_scratch_bytes = net->ort_scratch ? sb : 0;
+    }
+    if (!net->ort_cap || !net->ort_scratch ||
+        bridge_transfer_int32(net->ort_mats_dev, (const int32_t *)net->ort_mats.data(), nm * sizeof(KfOrthoMat) / 4)) {
+        set_err("constrain_orthonormal: alloc / upload of the matrix table");
+        return false;
+    }
+    net->ort_dirty = false;
+    return true;
+}
+
+extern "C" int nnet_constrain_orthonormal(KfNet *net) {
+    kf_take_pending(__func__);
+    if (!on_device(net, "constrain_orthonormal")) return -1;
+    if (!kf_orthonormal_constrain || !kf_orthonormal_scratch_bytes) {
+        set_err("constrain_orthonormal: this build of libkaldi_fp16 has no kf_orthonormal_constrain");
+        return -1;
+    }
+    if (net->ort_dirty && !upload_ortho_table(net)) return -1;
+    if (net->ort_mats.empty()) return 0;  // nothing is constrained: no launch
+    if (!ck(kf_orthonormal_constrain(net->master, net->w16, net->nparams, net->ort_mats.data(),
+                                     (const KfOrthoMat *)net->ort_mats_dev, (int)net->ort_mats.size(), net->ort_scratch,
+                                     net->ort_stats),
+            "constrain_orthonormal"))
+        return -1;
+    net->ort_ran = true;
+    net->wt_dirty = true;
+    // the MXFP8 weight copies follow every parameter change
+    return net->fp8 && !quantise_weights(net, false) ? -1 : 0;
+}
+
+extern "C" int nnet_orthonormal_stats(KfNet *net, float *scale, float *ratio, float *err, int n) {
+    if (!on_device(net, "orthonormal_stats")) return -1;
+    const int nm = (int)net->ort_mats.size();
+    if (!net->ort_ran || n < 0 || n > nm) {
+        set_err(net->ort_ran ? "orthonormal_stats: more components asked for than are constrained"
+                             : "orthonormal_stats: no nnet_constrain_orthonormal has run");
+        return -1;
+    }
+    // D2H through the bridge, ordered behind the call on the current stream (fp32 read = 2x
+    // fp16 count, as nnet_update_stats)
+    std::vector<float> st((size_t)4 * nm);
+    if (bridge_read_fp16((uint16_t *)st.data(), net->ort_stats, st.size() * 2)) {
+        set_err("orthonormal_stats: read");
+        return -1;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (scale) scale[i] = st[4 * i];
+        if (ratio) ratio[i] = st[4 * i + 1];
+        if (err) err[i] = st[4 * i + 2];
+    }
     return 0;
 }
 

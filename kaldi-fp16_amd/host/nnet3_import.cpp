@@ -41,6 +41,9 @@ struct Comp {
     float eps = 0, rms = 0;
     int nfi = 0, nfo = 0, hin = 0, hout = 0, heads = 0, kdim = 0, vdim = 0;
     float kscale = 0, lr = 0, maxc = 0, l2 = 0;
+    // <OrthonormalConstraint> of a TdnnComponent / LinearComponent line, when the line has one
+    bool has_orth = false;
+    float orth = 0;
 };
 
 // strings.Fields
@@ -173,6 +176,11 @@ Comp parse_header(const std::string &line) {
     c.kdim = tag_int(line, "<KeyDim>");
     c.vdim = tag_int(line, "<ValueDim>");
     c.kscale = tag_f32(line, "<KeyScale>");
+    if (c.type == "TdnnComponent" || c.type == "LinearComponent") {
+        std::string t;
+        bool re;
+        c.has_orth = tag_field(line, "<OrthonormalConstraint>", t) && parse_f32(t, c.orth, re);
+    }
     return c;
 }
 
@@ -389,6 +397,15 @@ int kf_nnet3_component(const KfNnet3Model *m, int idx, KfNnet3Component *o) {
     o->max_change = c.maxc;
     o->l2_regularize = c.l2;
     return 0;
+}
+
+int kf_nnet3_component_orthonormal(const KfNnet3Model *m, int idx, float *c) {
+    if (!m || idx < 0 || idx >= (int)m->comps.size()) {
+        set_err("kf_nnet3_component_orthonormal: bad index %d", idx);
+        return -1;
+    }
+    if (c) *c = m->comps[idx].has_orth ? m->comps[idx].orth : 0.f;
+    return m->comps[idx].has_orth ? 1 : 0;
 }
 
 }  // extern "C"
@@ -685,6 +702,8 @@ extern "C" int nnet_update_opts_from_kaldi(KfNet *net, const KfNnet3Model *m) {
     struct Opt {
         std::string name;
         float maxc, l2, lrf;
+        bool has_orth;
+        float orth;
     };
     std::vector<Opt> opts;
     const int nc = nnet_num_components(net);
@@ -704,11 +723,34 @@ extern "C" int nnet_update_opts_from_kaldi(KfNet *net, const KfNnet3Model *m) {
             set_err("%s: <MaxChange> %g and <L2Regularize> %g must be >= 0", nm, (double)c->maxc, (double)c->l2);
             return -1;
         }
-        opts.push_back(Opt{nm, c->maxc, c->l2, lrf});
+        // <OrthonormalConstraint>: taken only where the line has the tag. Kaldi writes a 0 on
+        // every TdnnComponent, the bias-carrying .affine included: nothing to set there. A
+        // value the net cannot take is an error before any option is set.
+        int first = 0, count = 0;
+        nnet_component_info(net, i, nullptr, 0, nullptr, nullptr, nullptr, &first, &count);
+        bool has_orth = c->has_orth;
+        if (has_orth) {
+            int rows = 0, cols = 0;
+            nnet_param_info(net, first, nullptr, 0, &rows, &cols, nullptr);
+            const bool matrix = count == 1 && rows > 1;
+            const bool shape = rows % 32 == 0 && cols % 32 == 0 && cols >= 32 && cols <= rows && cols <= 512;
+            if (!std::isfinite(c->orth) || (c->orth != 0.f && !(matrix && shape))) {
+                set_err("%s: <OrthonormalConstraint> %g on a component that cannot take it (%d tensors, %d x %d; "
+                        "transposed case not supported)", nm, (double)c->orth, count, rows, cols);
+                return -1;
+            }
+            if (!matrix) has_orth = false;
+        }
+        opts.push_back(Opt{nm, c->maxc, c->l2, lrf, has_orth, c->orth});
     }
     for (const Opt &o : opts)
         if (nnet_set_component_opts(net, o.name.c_str(), o.maxc, o.l2, o.lrf) != 0) {
             set_err("nnet_set_component_opts: %s", nnet_last_error() ? nnet_last_error() : "failed");
+            return -1;
+        }
+    for (const Opt &o : opts)
+        if (o.has_orth && nnet_set_component_orthonormal(net, o.name.c_str(), o.orth) != 0) {
+            set_err("nnet_set_component_orthonormal: %s", nnet_last_error() ? nnet_last_error() : "failed");
             return -1;
         }
     return 0;

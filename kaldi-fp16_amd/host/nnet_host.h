@@ -62,6 +62,10 @@ struct Layer {  // layers.go:12-120 (specs flattened)
     double key_scale = 0;  // 0 -> 1/sqrt(key_dim) (weight_loader.go:266-271)
     // update options of the layer's components (Kaldi's xconfig defaults; kf_nnet.h nnet_update)
     double max_change = 0.75, l2_regularize = 0, lr_factor = 1;
+    // orthonormal-constraint of the layer's .linear component (tdnnf, prefinal: default -1) or
+    // of a linear-component (default 0): 0 off, > 0 a fixed scale, < 0 the floating scale
+    // (kf_nnet.h nnet_constrain_orthonormal)
+    double orthonormal = 0;
 };
 
 bool ParseXConfig(const std::string &text, std::vector<LayerConfig> &out, std::string &err);

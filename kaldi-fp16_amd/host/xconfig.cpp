@@ -3,6 +3,7 @@
 // in C++ (the reference's host language, Go, is not available in this image).
 #include "nnet_host.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <sstream>
@@ -306,6 +307,20 @@ bool ResolveLayers(const std::vector<LayerConfig> &cfgs, std::vector<Layer> &lay
         if (!(L.max_change >= 0)) return fail("max-change must be >= 0, got " + cfg.get("max-change", ""));
         if (!(L.l2_regularize >= 0)) return fail("l2-regularize must be >= 0, got " + cfg.get("l2-regularize", ""));
         if (!(L.lr_factor > 0)) return fail("learning-rate-factor must be > 0, got " + cfg.get("learning-rate-factor", ""));
+        // orthonormal-constraint of the bottleneck / small projection / linear-component (Kaldi:
+        // tdnnf and prefinal hard-wire -1 on their .linear, a linear-component defaults to 0);
+        // on any other layer kind the key does not apply and is not read
+        if (cfg.type == LayerType::TDNNF || cfg.type == LayerType::Prefinal || cfg.type == LayerType::Linear) {
+            L.orthonormal = cfg.type == LayerType::Linear ? 0.0 : -1.0;
+            auto it = cfg.params.find("orthonormal-constraint");
+            if (it != cfg.params.end()) {
+                char *end = nullptr;
+                const double v = strtod(it->second.c_str(), &end);
+                if (it->second.empty() || !end || *end != 0 || !std::isfinite(v))
+                    return fail("orthonormal-constraint must be a finite number, got \"" + it->second + "\"");
+                L.orthonormal = v;
+            }
+        }
         layers.push_back(L);
     }
     return true;

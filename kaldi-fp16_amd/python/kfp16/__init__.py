@@ -146,6 +146,11 @@ _sig(nnet, "nnet_component_info", _i, _vp, _i, C.c_char_p, _i, _fp, _fp, _fp, C.
 _sig(nnet, "nnet_set_component_opts", _i, _vp, C.c_char_p, _f, _f, _f)
 _sig(nnet, "nnet_update", _i, _vp, _f, _f, _f, _f)
 _sig(nnet, "nnet_update_stats", _i, _vp, _vp, _vp, _i, _fp, _fp)
+_sig(nnet, "nnet_component_orthonormal", _i, _vp, _i, _fp)
+_sig(nnet, "nnet_set_component_orthonormal", _i, _vp, C.c_char_p, _f)
+_sig(nnet, "nnet_orthonormal_components", _i, _vp, C.POINTER(_i), _i)
+_sig(nnet, "nnet_constrain_orthonormal", _i, _vp)
+_sig(nnet, "nnet_orthonormal_stats", _i, _vp, _vp, _vp, _vp, _i)
 _sig(nnet, "nnet_bind_grad_buffer", _i, _vp, _vp)
 _sig(nnet, "nnet_backward_n", _i, _vp, _vp, _i)
 _sig(nnet, "nnet_debug_tensor", _vp, _vp, C.c_char_p, _i)
@@ -466,6 +471,44 @@ class Network:
               "nnet_update_stats")
         return dict(norms=norms, scales=scales, global_norm=gn.value, global_scale=gs.value)
 
+    # Semi-orthogonal constraint (kf_nnet.h nnet_constrain_orthonormal) -------
+    def component_orthonormal(self, name: str) -> float:
+        """A component's orthonormal-constraint value: 0 off, > 0 a fixed scale, < 0 floating."""
+        c = _f()
+        for i, comp in enumerate(self.components()):
+            if comp["name"] == name:
+                check(nnet.nnet_component_orthonormal(self.h, i, C.byref(c)), "nnet_component_orthonormal")
+                return c.value
+        raise KeyError(name)
+
+    def set_component_orthonormal(self, name: str, c: float):
+        """Override a component's orthonormal-constraint value (its tensor must be one weight
+        matrix [K x n] with K, n multiples of 32, 32 <= n <= K, n <= 512 unless c is 0)."""
+        check(nnet.nnet_set_component_orthonormal(self.h, name.encode(), float(c)), "nnet_set_component_orthonormal")
+
+    def orthonormal_components(self) -> list:
+        """Names of the constrained components (value != 0), in components() order."""
+        n = nnet.nnet_orthonormal_components(self.h, None, 0)
+        idx = (_i * max(n, 1))()
+        nnet.nnet_orthonormal_components(self.h, idx, n)
+        comps = self.components()
+        return [comps[idx[k]]["name"] for k in range(n)]
+
+    def constrain_orthonormal(self):
+        """One application of Kaldi's ConstrainOrthonormal to every constrained component
+        (master and fp16 weights; the velocity is not touched)."""
+        check(nnet.nnet_constrain_orthonormal(self.h), "nnet_constrain_orthonormal")
+
+    def orthonormal_stats(self) -> dict:
+        """The last constrain_orthonormal's report (synchronises), measured before its update:
+        names, and per constrained component scale s, ratio and err = |W^T W - s^2 I|_F."""
+        names = self.orthonormal_components()
+        n = len(names)
+        s, r, e = (np.empty(n, np.float32) for _ in range(3))
+        check(nnet.nnet_orthonormal_stats(self.h, s.ctypes.data, r.ctypes.data, e.ctypes.data, n),
+              "nnet_orthonormal_stats")
+        return dict(names=names, scale=s, ratio=r, err=e)
+
     def dp_plan(self, bucket_bytes: int, max_buckets: int = 256):
         """[(after_step, begin, end)]: the gradient buckets nnet_backward exchanges
         (kf_nnet.h nnet_dp_plan), in issue order."""
@@ -629,6 +672,14 @@ class KfUpdComp(C.Structure):
 UPD_CHUNK = 4096  # kf_ops.h KF_UPD_CHUNK
 _sig(core, "kf_update_scratch_bytes", _ll, _ll, _i, _i)
 _sig(core, "kf_update_maxchange", _i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp, _vp)
+
+
+class KfOrthoMat(C.Structure):
+    _fields_ = [("offset", _ll), ("K", _i), ("n", _i), ("c", _f), ("reserved", _i)]
+
+
+_sig(core, "kf_orthonormal_scratch_bytes", _ll, _vp, _i)
+_sig(core, "kf_orthonormal_constrain", _i, _vp, _vp, _ll, _vp, _vp, _i, _vp, _vp)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows_from", _i, _vp, _vp, _ll, _i, _i, _i, _i)

@@ -47,6 +47,7 @@ _sig("kf_nnet3_find", _i, _vp, C.c_char_p)
 _sig("nnet_load_kaldi", _i, _vp, _vp, _i, C.POINTER(KfLoadStats))
 _sig("nnet_set_idct", _i, _vp, C.c_char_p, _vp, _i, _i)
 _sig("nnet_update_opts_from_kaldi", _i, _vp, _vp)
+_sig("kf_nnet3_component_orthonormal", _i, _vp, _i, C.POINTER(C.c_float))
 
 
 class ModelError(KfError):
@@ -127,6 +128,18 @@ class Nnet3Model:
                          c.target_rms, c.num_filters_in, c.num_filters_out, c.height_in, c.height_out,
                          c.learning_rate, c.max_change, c.l2_regularize)
 
+    def orthonormal_constraint(self, name: str):
+        """<OrthonormalConstraint> of a TdnnComponent / LinearComponent, None when its line has
+        no such tag (kf_model.h kf_nnet3_component_orthonormal)."""
+        i = nnet.kf_nnet3_find(self._h, name.encode())
+        if i < 0:
+            raise KeyError(name)
+        c = C.c_float()
+        r = nnet.kf_nnet3_component_orthonormal(self._h, i, C.byref(c))
+        if r < 0:
+            raise ModelError(last_error())
+        return c.value if r else None
+
     def __getitem__(self, name: str) -> Component:
         i = nnet.kf_nnet3_find(self._h, name.encode())
         if i < 0:
@@ -148,7 +161,8 @@ class Nnet3Model:
 
     def update_opts_into(self, net) -> None:
         """Each update component's max-change and l2-regularize from the model's component of
-        the same name (kf_model.h nnet_update_opts_from_kaldi); learning rates are not taken."""
+        the same name (kf_model.h nnet_update_opts_from_kaldi); learning rates are not taken.
+        The orthonormal constraint is taken where the model's line has the tag."""
         if nnet.nnet_update_opts_from_kaldi(net.h, self._h) != 0:
             raise ModelError(last_error())
 

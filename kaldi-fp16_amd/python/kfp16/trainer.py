@@ -10,6 +10,8 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
   4. optimizer.Update per tensor  -> Network.sgd over the flat buffer (optimize.go:95-142),
                                      or with TrainConfig.kaldi_update Network.update: Kaldi's
                                      per-component max-change, L2 and learning-rate factors
+  5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
+                                     ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
 
 The numerator FSTs come from the batch's per-sequence CSRs (TrainingBatch.PerSeqCSRs),
@@ -46,6 +48,11 @@ class TrainConfig:
     kaldi_update: bool = False
     max_param_change: float = 0.0
     l2_scale: float | None = None
+    # orthonormal_every: N > 0 applies the semi-orthogonal constraint (Network.constrain_orthonormal,
+    # Kaldi's ConstrainOrthonormal) after the parameter update of every N-th step, with either
+    # update; Kaldi handles each component at one update in four on average, which is N = 4.
+    # 0: never, as before.
+    orthonormal_every: int = 0
 
 
 def chain_rows(frame_offsets, num_frames, frames_per_seq, subsampling: int, left_context: int):
@@ -83,6 +90,7 @@ class EgsTrainer:
         self.ivec_dim = int(m.group(1)) if m else 0
         self.ivec = DeviceBuffer(max_egs * self.ivec_dim * 2) if self.ivec_dim else None
         self.max_egs = max_egs
+        self.steps = 0  # steps taken
 
     def step(self, batch, allreduce=None):
         """One TrainStep on `batch` (kfp16.egs.TrainingBatch). allreduce: optional callable
@@ -119,6 +127,9 @@ class EgsTrainer:
             self.net.update(self.cfg.learning_rate, self.cfg.momentum, self.cfg.max_param_change, l2_scale)
         else:
             self.net.sgd(self.cfg.learning_rate, self.cfg.momentum)
+        self.steps += 1
+        if self.cfg.orthonormal_every > 0 and self.steps % self.cfg.orthonormal_every == 0:
+            self.net.constrain_orthonormal()
 
     def result(self):
         sync()
