@@ -78,8 +78,9 @@ typedef struct {
     int mask_rows;             /* source rows the mask covers */
     /* time-strided rows (a conv evaluated on a subset of its output frames, the row-
      * subsampled step's last conv): st = t0 + t*tmul + dt[p] in the rule above. 0 / 0 =
-     * the plain rule. Only the A operand of a kf_gemm_fused convolution that runs on the
-     * halo kernel takes it; other uses fail. */
+     * the plain rule. Only the A operand of a convolution that runs on a halo kernel takes
+     * it: kf_gemm_fused's im2col operand (forward) and kf_gemm_wgrad's (weight gradient over
+     * the strided output frames); other uses fail. */
     int tmul, t0;
 } KfOperand;
 
@@ -411,6 +412,16 @@ int kf_transpose_batch(int n, const void *const *src, void *const *dst, const in
  * number `at` counted from this call: [0] start, [1 + 2s] after step s's wait and barrier,
  * [2 + 2s] after its MFMAs, [126] before the epilogue, [127] end; buf NULL disarms */
 void kf_halo_trace(unsigned long long *buf, int at);
+/* diagnostics (tests): what the calling thread's last halo dispatch chose, read-only (no
+ * launch depends on it). out[0] = 0 none yet, 1 the last kf_gemm_fused that reached the conv
+ * halo dispatch, 2 the last kf_gemm_wgrad that reached the halo weight gradient's; out[1] = 1
+ * when the halo kernel was launched, 0 when the dispatch declined (the rest is then zero).
+ *   kind 1: out[2..] = BM, BN, BROW (B as shifted weight rows), nch (64-channel chunks),
+ *           nbuf (halo images), hpe, hpos (halo row pitch), pitch pad taken, row tiles,
+ *           column tiles
+ *   kind 2: out[2..] = BN, waves, stages, npieces, hpw, splits, kps
+ * Writes min(n, 16) ints (unused ones zero) and returns that count. */
+int kf_halo_debug_last(int *out, int n);
 /* diagnostics: phase stamps of block `blk` and {start, end, hw id | xcc << 32} of every
  * block of gemm_kernel launch number `at` (counted from this call), wall_clock64 ticks
  * (100 MHz); buf holds 64 + 3 * blocks words; null = off */

@@ -264,6 +264,7 @@ void kf_prof_stop(int idx);
 int kf_conv_wgrad_halo_try(int M, int N, int K, const OpD &a, const OpD &b, float *dW, long long ldw,
                            float *bias_grad, int accumulate) {
     kf_take_pending(__func__);
+    int *const dbg = kf_halo_dbg_begin(2);
     if (a.nparts != WTAPS || a.pw % 64 || a.simple || a.edges || a.tclamp || a.hshift ||
         a.hmul < 1 || a.hmul > 2 || a.hout < 2 || a.ncols != WTAPS * a.pw || M != a.ncols ||
         a.nrows != K || !b.simple || b.nrows != K || b.ncols != N || N % 64)
@@ -346,6 +347,10 @@ int kf_conv_wgrad_halo_try(int M, int N, int K, const OpD &a, const OpD &b, floa
     const int prof = kf_prof_start2(5, 2.0 * M * N * (double)K,
                                     (double)a.T * a.hsrc * a.pw * 2.0 + (double)K * N * 2.0 + (double)M * N * 4.0);
     const dim3 grid(tiles * H.splits);
+    {
+        const int v[] = {2, 1, BN, nw, ns, H.npieces, H.hpw, H.splits, H.kps};
+        std::copy(v, v + sizeof v / sizeof v[0], dbg);
+    }
     if (BN == 128) {
         if (ns == 3) conv_wgrad_halo_kernel<128, 8, 3><<<grid, 512, lds, kf_stream()>>>(b, H);
         else conv_wgrad_halo_kernel<128, 8, 2><<<grid, 512, lds, kf_stream()>>>(b, H);

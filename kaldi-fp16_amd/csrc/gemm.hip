@@ -1268,6 +1268,18 @@ extern "C" void kf_halo_trace(unsigned long long *buf, int at) {
     g_halo_trace_at = at;
     g_halo_launches = 0;
 }
+// diagnostics: the geometry of the calling thread's last halo dispatch (kf_halo_debug_last)
+static thread_local int g_halo_dbg[KF_HALO_DBG_N];
+int *kf_halo_dbg_begin(int kind) {
+    memset(g_halo_dbg, 0, sizeof g_halo_dbg);
+    g_halo_dbg[0] = kind;
+    return g_halo_dbg;
+}
+extern "C" int kf_halo_debug_last(int *out, int n) {
+    const int m = std::min(std::max(n, 0), KF_HALO_DBG_N);
+    for (int i = 0; out && i < m; ++i) out[i] = g_halo_dbg[i];
+    return out ? m : 0;
+}
 template <int BM, int BN, int WM, int WN, bool BKC, int BMODE, bool BROW, int ST>
 static int launch_halo(int M, int N, const OpD &B, const KfEpilogue &E, const HaloArgs &H0, size_t lds) {
     kf_take_pending(__func__);
@@ -1303,6 +1315,7 @@ static int launch_halo(int M, int N, const OpD &B, const KfEpilogue &E, const Ha
 
 static int conv_halo_try(int M, int N, int K, const OpD &a, const OpD &b, int bm, bool bkc,
                          const KfEpilogue &E) {
+    int *const dbg = kf_halo_dbg_begin(1);
     if (op_mode(a) != OP_GEN || !a.p64 || a.edges || a.tclamp || a.hshift ||
         a.hmul < 1 || a.hmul > 2 || a.hout < 2 || a.ncols != K || a.nparts * a.pw != K)
         return 0;
@@ -1403,6 +1416,11 @@ static int conv_halo_try(int M, int N, int K, const OpD &a, const OpD &b, int bm
         const int x = a.dh[p] + H.pad;
         H.ctap[p] = (a.dt[p] - dtmin) * H.hpos + (x % a.hmul) * H.hpe + x / a.hmul;
         H.bshift[p] = brow ? b.dt[p] : 0;
+    }
+    {
+        const int v[] = {1, 1, BM_, BN_, brow, H.nch, H.nbuf, H.hpe, H.hpos, pad8, (M + BM_ - 1) / BM_,
+                         (N + BN_ - 1) / BN_};
+        std::copy(v, v + sizeof v / sizeof v[0], dbg);
     }
     // (measured and dropped: a 4-stage weight ring at one workgroup per CU, cnn2 517 ->
     // 884 us; 64-column tiles on two 128x64-tile waves, cnn2 529 -> 781 us)

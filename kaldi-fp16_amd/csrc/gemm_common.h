@@ -32,8 +32,15 @@ struct OpD {
     // e.g. an edge row) are unmasked
     const uint8_t *mk;
     unsigned mlim;
-    int tmul, t0;       // time-strided rows (KfOperand.tmul / t0; conv halo forward only)
+    int tmul, t0;       // time-strided rows (KfOperand.tmul / t0): the A operand of the conv halo
+                        // kernels only (forward / input gradient and weight gradient)
 };
+
+// kf_halo_debug_last's record (kf_ops.h): what the calling thread's last conv_halo_try
+// (kind 1) / kf_conv_wgrad_halo_try (kind 2) chose. v[0] = kind, v[1] = taken, then the
+// fields in kf_ops.h's order. Host only; never read by a launch.
+constexpr int KF_HALO_DBG_N = 16;
+int *kf_halo_dbg_begin(int kind);  // zeroes the record, sets v[0] = kind; returns v
 
 // compile-time loop: body(I) with I a std::integral_constant (forces full unrolling,
 // so register arrays are never indexed dynamically and never fall to scratch)

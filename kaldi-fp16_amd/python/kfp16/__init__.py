@@ -299,6 +299,22 @@ def prof_records(max_n: int = 4096):
                  tile=mnkt[4 * i + 3]) for i in range(n)]
 
 
+def halo_debug_last() -> dict:
+    """kf_halo_debug_last: what the calling thread's last conv halo dispatch chose. kind
+    'fused' (forward / input gradient) or 'wgrad', taken, and that kind's geometry"""
+    v = (_i * 16)()
+    core.kf_halo_debug_last(v, 16)
+    if v[0] == 1:
+        names = ("BM", "BN", "brow", "nch", "nbuf", "hpe", "hpos", "pad", "mtiles", "ntiles")
+    elif v[0] == 2:
+        names = ("BN", "waves", "stages", "npieces", "hpw", "splits", "kps")
+    else:
+        return dict(kind=None, taken=0)
+    d = dict(kind="fused" if v[0] == 1 else "wgrad", taken=v[1])
+    d.update({k: v[2 + i] for i, k in enumerate(names)})
+    return d
+
+
 def set_stream(stream_handle) -> None:
     core.kf_set_stream(C.c_void_p(stream_handle) if stream_handle else None)
 
@@ -651,6 +667,7 @@ _sig(core, "kf_gemm_wgrad_scaled", _i, _i, _i, _i, C.POINTER(KfOperand), C.POINT
 _sig(core, "kf_gemm_wgrad_target", _i, _i)
 _sig(core, "kf_gemm_debug_kil", None, _i)
 _sig(core, "kf_gemm_trace", None, _vp, _i, _i)
+_sig(core, "kf_halo_debug_last", _i, C.POINTER(_i), _i)
 _sig(core, "kf_quant_mxfp8", _i, _vp, _ll, _i, _i, _i, _vp, _ll, _vp, _ll)
 # non-MFMA layer pieces (csrc/layers.hip) and the ivector input path (csrc/ivector.hip)
 _ip = C.POINTER(_i)
