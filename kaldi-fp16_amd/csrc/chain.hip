@@ -22,6 +22,7 @@
 // The C-ABI of chain.h / chain_den.h / chain_backward_api.h is served by the same
 // kernels; kf_chain.h is the batched, device-resident product interface.
 #include "kf_common.h"
+#include "kf_prof.h"
 #include "../../include/chain.h"
 #include "../../include/chain_backward_api.h"
 #include "../../include/chain_den.h"

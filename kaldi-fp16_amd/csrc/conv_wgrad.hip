@@ -14,11 +14,11 @@
 // LDS read (ds_read_b64_tr_b16) at a per-tap row offset, each lane addressing the
 // halo row of its own output rows. B (dZ rows) streams through the usual
 // reduction-major stager. Split over the reduction into fp32 slabs like kf_gemm_wgrad;
-// the slab reduce is gemm.hip's.
-#include <algorithm>
+// the slab reduce is gemm_wgrad.hip's.
 #include <cstdlib>
 
-#include "gemm_common.h"
+#include "gemm_host.h"
+#include "kf_prof.h"
 
 namespace {
 
@@ -33,29 +33,6 @@ constexpr int WROWS = WTAPS * 64;
 __device__ __forceinline__ int hsw(int R) { return (((R >> 1) & 1) | (((R >> 3) & 1) << 1)) << 1; }
 
 constexpr int HPW_MAX = 8;       // halo pieces per wave per K-step (host-checked)
-
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the immediate is compile-time)
-__device__ __forceinline__ void wait_vmcnt_rt(int n) {
-    switch (n) {
-        case 0: wait_vmcnt<0>(); break;
-        case 1: wait_vmcnt<1>(); break;
-        case 2: wait_vmcnt<2>(); break;
-        case 3: wait_vmcnt<3>(); break;
-        case 4: wait_vmcnt<4>(); break;
-        case 5: wait_vmcnt<5>(); break;
-        case 6: wait_vmcnt<6>(); break;
-        case 7: wait_vmcnt<7>(); break;
-        case 8: wait_vmcnt<8>(); break;
-        case 9: wait_vmcnt<9>(); break;
-        case 10: wait_vmcnt<10>(); break;
-        case 11: wait_vmcnt<11>(); break;
-        case 12: wait_vmcnt<12>(); break;
-        case 13: wait_vmcnt<13>(); break;
-        case 14: wait_vmcnt<14>(); break;
-        case 15: wait_vmcnt<15>(); break;
-        default: wait_vmcnt<0>(); break;
-    }
-}
 
 struct WHalo {
     const h16 *x;        // source [T x hsrc x fin] (row = frame, ld elements)
@@ -253,33 +230,28 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_wgrad_halo_kernel(OpD B,
 
 }  // namespace
 
-// defined in gemm.hip
-void kf_wgrad_reduce(const float *slab, const float *bias_slab, int splits, int M, int N, float *dW,
-                     long long ldw, float *bias_grad, int accumulate, const float *cs = nullptr);
-int kf_prof_start2(int cls, double flops, double bytes);
-void kf_prof_stop(int idx);
+// What conv_wgrad_halo_kernel would run for one weight gradient (the slab pointers of H are
+// the dispatch's to fill)
+struct WHaloPlan {
+    int BN, nw, ns;  // column tile, waves, ring stages
+    WHalo H;
+    size_t lds;      // dynamic LDS bytes
+};
 
-// Returns 1 when launched, 0 when the operands are not a 3x3 conv im2col pair this
-// kernel covers (the caller runs the im2col GEMM), -1 on error.
-int kf_conv_wgrad_halo_try(int M, int N, int K, const OpD &a, const OpD &b, float *dW, long long ldw,
-                           float *bias_grad, int accumulate) {
-    kf_take_pending(__func__);
+// The plan for (M, N, K, a, b), or false when the operands are not a 3x3 conv im2col pair this
+// kernel covers. Pure: no HIP call, nothing written but P and the calling thread's
+// kf_halo_debug_last record.
+static bool conv_wgrad_halo_plan(int M, int N, int K, const OpD &a, const OpD &b, WHaloPlan &P) {
     int *const dbg = kf_halo_dbg_begin(2);
     if (a.nparts != WTAPS || a.pw % 64 || a.simple || a.edges || a.tclamp || a.hshift ||
         a.hmul < 1 || a.hmul > 2 || a.hout < 2 || a.ncols != WTAPS * a.pw || M != a.ncols ||
         a.nrows != K || !b.simple || b.nrows != K || b.ncols != N || N % 64)
-        return 0;
+        return false;
     // 64-column tiles on 4-wave workgroups, two per CU, measured faster than 128-column
     // tiles on 8 waves for every layer (cnn6 1330 -> 1238 us, cnn4 690 -> 640 us)
     int BN = 64;
-    int dtmin = 1 << 20, dtmax = -(1 << 20), dhmin = 1 << 20, dhmax = -(1 << 20);
-    for (int p = 0; p < WTAPS; ++p) {
-        dtmin = std::min(dtmin, a.dt[p]);
-        dtmax = std::max(dtmax, a.dt[p]);
-        dhmin = std::min(dhmin, a.dh[p]);
-        dhmax = std::max(dhmax, a.dh[p]);
-    }
-    WHalo H;
+    const TapGeom tg = tap_geometry(a);
+    WHalo &H = P.H;
     memset(&H, 0, sizeof H);
     H.x = a.base;
     H.ld = a.ld;
@@ -288,76 +260,80 @@ int kf_conv_wgrad_halo_try(int M, int N, int K, const OpD &a, const OpD &b, floa
     H.hmul = a.hmul;
     H.hsrc = a.hsrc;
     H.fin = a.pw;
-    H.pad = std::max(0, -dhmin);
-    const int maxshp = (a.hout - 1) * a.hmul + dhmax + H.pad;
-    const int HP = std::max(a.hsrc + H.pad, maxshp + 1);
-    H.hpe = (HP + a.hmul - 1) / a.hmul;
+    H.pad = tg.pad;
+    H.hpe = tg.hpe;
     H.hpos = H.hpe * a.hmul;
-    H.dtmin = dtmin;
+    H.dtmin = tg.dtmin;
     H.ts = a.tmul;
     H.toff = a.t0;
     // frames a 64-row K-step touches (its first row's frame + the rows' span, ts apart) + the
     // time taps
-    H.nf = H.ts * ((BK - 1 + a.hout - 1) / a.hout) + 1 + (dtmax - dtmin);
+    H.nf = H.ts * ((BK - 1 + a.hout - 1) / a.hout) + 1 + (tg.dtmax - tg.dtmin);
     H.rows = H.nf * H.hpos;
     H.npieces = (H.rows + 7) / 8;
     H.halo_bytes = H.npieces * 1024;
     H.inv_hout = (65536u + a.hout - 1) / a.hout;
-    if ((long long)(a.hout + 2 * BK) * a.hout >= 65536) return 0;  // the 16-bit division
-    for (int p = 0; p < WTAPS; ++p) {
-        const int x = a.dh[p] + H.pad;
-        H.ctap[p] = (a.dt[p] - dtmin) * H.hpos + (x % a.hmul) * H.hpe + x / a.hmul;
-    }
+    if ((long long)(a.hout + 2 * BK) * a.hout >= 65536) return false;  // the 16-bit division
+    tap_rows(a, tg, H.hpe, H.ctap);
     H.mout = K;
     // BN = 64: 4-wave workgroups, two per CU; BN = 128: 8 waves, one per CU.
-    // Stages: 3 where they fit in LDS, else 2.
+    // Stages: 3 where they fit in LDS (BN = 64 only), else 2.
     // a halo too large for 4 waves' registers (cnn3: 37 pieces) takes the 8-wave form
     if (BN == 64 && (H.npieces + 3) / 4 > HPW_MAX && N % 128 == 0) BN = 128;
     const int nw = BN == 64 ? 4 : 8;
     H.hpw = (H.npieces + nw - 1) / nw;
-    if (H.hpw > HPW_MAX || H.nf >= 2048 || (long long)a.hsrc * a.pw * 2 >= (1 << 20)) return 0;
+    if (H.hpw > HPW_MAX || H.nf >= 2048 || (long long)a.hsrc * a.pw * 2 >= (1 << 20)) return false;
     const size_t stage = (size_t)H.halo_bytes + (size_t)BN * BK * 2;
     const size_t cap = BN == 64 ? 80 * 1024 : 160 * 1024;  // BN = 64: leave room for 2 per CU
     // (8-wave tiles: 2 stages, measured faster than 3)
     const int ns = BN == 64 && 3 * stage + 1024 <= cap ? 3 : 2;
-    const size_t lds = ns * stage + 1024;
-    if (lds > 160 * 1024 || (ns - 2) * (H.hpw + BN / 8 / nw) > 15) return 0;
-    if (((long long)a.T * a.ld + (long long)a.hsrc * a.pw) * 2 >= (1LL << 32) - 64) return 0;
+    P.lds = ns * stage + 1024;
+    if (P.lds > 160 * 1024 || (ns - 2) * (H.hpw + BN / 8 / nw) > 15) return false;
+    if (((long long)a.T * a.ld + (long long)a.hsrc * a.pw) * 2 >= (1LL << 32) - 64) return false;
     H.ctiles = a.pw / 64;
     H.ntiles = N / BN;
     const int tiles = H.ctiles * H.ntiles;
     const int nks = (K + BK - 1) / BK;
     // one workgroup per CU: split the reduction so the grid is about one full wave of CUs
-    const int target = nw == 4 && lds <= 80 * 1024 ? 512 : 256;
+    const int target = nw == 4 && P.lds <= 80 * 1024 ? 512 : 256;
     int splits = std::max(1, (target + tiles - 1) / tiles);
     splits = std::min(splits, std::max(1, nks / 8));
     H.kps = (nks + splits - 1) / splits;
     H.splits = (nks + H.kps - 1) / H.kps;
     H.Mtot = M;
     H.N = N;
+    P.BN = BN;
+    P.nw = nw;
+    P.ns = ns;
+    const int v[] = {2, 1, BN, nw, ns, H.npieces, H.hpw, H.splits, H.kps};
+    std::copy(v, v + sizeof v / sizeof v[0], dbg);
+    return true;
+}
+
+// Returns 1 when launched, 0 when the plan does not apply (the caller runs the im2col
+// GEMM), -1 on error.
+int kf_conv_wgrad_halo_try(int M, int N, int K, const OpD &a, const OpD &b, float *dW, long long ldw,
+                           float *bias_grad, int accumulate) {
+    kf_take_pending(__func__);
+    WHaloPlan P;
+    if (!conv_wgrad_halo_plan(M, N, K, a, b, P)) return 0;
+    WHalo &H = P.H;
     const size_t slab_bytes = (size_t)H.splits * M * N * 4;
     const size_t bias_bytes = bias_grad ? (size_t)H.splits * N * 4 : 0;
     char *ws = (char *)kf_workspace_stream(slab_bytes + bias_bytes + 256);
     if (!ws) {
+        kf_halo_dbg_begin(2);  // nothing was taken
         kf_report_error("conv wgrad: workspace allocation of %zu bytes failed", slab_bytes + bias_bytes);
         return -1;
     }
     H.slab = (float *)ws;
     H.bias_slab = bias_grad ? (float *)(ws + ((slab_bytes + 255) & ~(size_t)255)) : nullptr;
-    const int prof = kf_prof_start2(5, 2.0 * M * N * (double)K,
+    const int prof = kf_prof_start2(KF_PROF_HALO_WGRAD, 2.0 * M * N * (double)K,
                                     (double)a.T * a.hsrc * a.pw * 2.0 + (double)K * N * 2.0 + (double)M * N * 4.0);
-    const dim3 grid(tiles * H.splits);
-    {
-        const int v[] = {2, 1, BN, nw, ns, H.npieces, H.hpw, H.splits, H.kps};
-        std::copy(v, v + sizeof v / sizeof v[0], dbg);
-    }
-    if (BN == 128) {
-        if (ns == 3) conv_wgrad_halo_kernel<128, 8, 3><<<grid, 512, lds, kf_stream()>>>(b, H);
-        else conv_wgrad_halo_kernel<128, 8, 2><<<grid, 512, lds, kf_stream()>>>(b, H);
-    } else {
-        if (ns == 3) conv_wgrad_halo_kernel<64, 4, 3><<<grid, 256, lds, kf_stream()>>>(b, H);
-        else conv_wgrad_halo_kernel<64, 4, 2><<<grid, 256, lds, kf_stream()>>>(b, H);
-    }
+    const dim3 grid(H.ctiles * H.ntiles * H.splits);
+    if (P.BN == 128) conv_wgrad_halo_kernel<128, 8, 2><<<grid, 512, P.lds, kf_stream()>>>(b, H);
+    else if (P.ns == 3) conv_wgrad_halo_kernel<64, 4, 3><<<grid, 256, P.lds, kf_stream()>>>(b, H);
+    else conv_wgrad_halo_kernel<64, 4, 2><<<grid, 256, P.lds, kf_stream()>>>(b, H);
     kf_prof_stop(prof);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -1,7 +1,7 @@
-// gemm_common.h — device pieces shared by the MFMA GEMM kernels (gemm.hip, conv_wgrad.hip):
-// operand addressing (the device form of KfOperand), the LDS images and fragment
-// loads of v_mfma_f32_16x16x32_f16, the LDS-DMA operand stager and the 8-column
-// epilogue. gfx950 only.
+// gemm_common.h — device pieces shared by the MFMA kernels (gemm_kernel.h, conv_halo.hip,
+// conv_wgrad.hip) and the MXFP8 quantisers: operand addressing (the device form of
+// KfOperand), the LDS images and fragment loads of v_mfma_f32_16x16x32_f16, the LDS-DMA
+// operand stager, the 8-column epilogue and the e4m3 / E8M0 conversions. gfx950 only.
 #pragma once
 #include <utility>
 
@@ -35,12 +35,6 @@ struct OpD {
     int tmul, t0;       // time-strided rows (KfOperand.tmul / t0): the A operand of the conv halo
                         // kernels only (forward / input gradient and weight gradient)
 };
-
-// kf_halo_debug_last's record (kf_ops.h): what the calling thread's last conv_halo_try
-// (kind 1) / kf_conv_wgrad_halo_try (kind 2) chose. v[0] = kind, v[1] = taken, then the
-// fields in kf_ops.h's order. Host only; never read by a launch.
-constexpr int KF_HALO_DBG_N = 16;
-int *kf_halo_dbg_begin(int kind);  // zeroes the record, sets v[0] = kind; returns v
 
 // compile-time loop: body(I) with I a std::integral_constant (forces full unrolling,
 // so register arrays are never indexed dynamically and never fall to scratch)
@@ -378,6 +372,58 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt");
     __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
+}
+// s_waitcnt vmcnt(n) for a wave-uniform run-time n <= 15 (the immediate is compile-time)
+__device__ __forceinline__ void wait_vmcnt_rt(int n) {
+    switch (n) {
+        case 0: wait_vmcnt<0>(); break;
+        case 1: wait_vmcnt<1>(); break;
+        case 2: wait_vmcnt<2>(); break;
+        case 3: wait_vmcnt<3>(); break;
+        case 4: wait_vmcnt<4>(); break;
+        case 5: wait_vmcnt<5>(); break;
+        case 6: wait_vmcnt<6>(); break;
+        case 7: wait_vmcnt<7>(); break;
+        case 8: wait_vmcnt<8>(); break;
+        case 9: wait_vmcnt<9>(); break;
+        case 10: wait_vmcnt<10>(); break;
+        case 11: wait_vmcnt<11>(); break;
+        case 12: wait_vmcnt<12>(); break;
+        case 13: wait_vmcnt<13>(); break;
+        case 14: wait_vmcnt<14>(); break;
+        case 15: wait_vmcnt<15>(); break;
+        default: wait_vmcnt<0>(); break;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// MXFP8 conversions (the GEMM epilogue's copy and the quantisers)
+// ---------------------------------------------------------------------------
+// e4m3 (OCP) of 8 values already divided by the block scale; clamp at 448 first
+// (v_cvt_pk_fp8_f32 rounds 464..479 to 448 but 480 and above to NaN)
+__device__ __forceinline__ uint2 pack_e4m3x8(const float *v) {
+    uint2 r;
+    unsigned w[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        float c[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) c[e] = fminf(fmaxf(v[4 * h + e], -448.f), 448.f);
+        unsigned x = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
+        x = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], x, true);
+        w[h] = x;
+    }
+    r.x = w[0];
+    r.y = w[1];
+    return r;
+}
+
+// E8M0 exponent of a block with max magnitude amax: floor(log2 amax) - 8,
+// clamped so that 2^-e stays a normal float; amax = 0 -> 0
+__device__ __forceinline__ int mx_exponent(float amax) {
+    if (!(amax > 0.f)) return 0;
+    const int ex = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127;
+    return min(max(ex - 8, -126), 126);
 }
 
 // ---------------------------------------------------------------------------

@@ -42,15 +42,12 @@ hipStream_t kf_stream();
 // top of every entry that checks its own launches with hipGetLastError()
 extern "C" int kf_take_pending(const char *where);
 
-// sets the kf_last_error() text from another module (gemm.hip owns the slot)
+// sets the kf_last_error() text (kf_ops.h) from any module; gemm_host.hip owns the slot
 void kf_report_error(const char *fmt, ...);
 
-// kf_prof_* timing of a launch bracket on the current stream (gemm.hip);
-// classes: 0 fused GEMM, 1 wgrad GEMM, 2 chain numerator, 3 chain denominator,
-// 4 conv halo fwd / dX, 5 conv halo wgrad, 6 slab reduce (include/kf_ops.h)
-enum { KF_PROF_CHAIN_NUM = 2, KF_PROF_CHAIN_DEN = 3 };
-int kf_prof_start(int cls, double work);
-void kf_prof_stop(int idx);
+// the reference-ABI GEMM behind ops_gemm / ops_gemm_batched (gemm_abi.hip, called by ops.hip)
+int kf_ops_gemm_impl(int M, int N, int K, float alpha, const void *A, int lda, const void *B, int ldb,
+                     float beta, void *C, int ldc, char *err, size_t errlen);
 
 // persistent per-device scratch (never freed; grows monotonically)
 void *kf_workspace(size_t bytes, int slot);

@@ -10,9 +10,6 @@
 
 KF_DECLARE_ERR(ops)
 
-int kf_ops_gemm_impl(int M, int N, int K, float alpha, const void *A, int lda, const void *B,
-                     int ldb, float beta, void *C, int ldc, char *err, size_t errlen);
-
 static int ops_check(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -1,4 +1,4 @@
-"""conv_halo_kernel (csrc/gemm.hip: forward and input gradient) and conv_wgrad_halo_kernel
+"""conv_halo_kernel (csrc/conv_halo.hip: forward and input gradient) and conv_wgrad_halo_kernel
 (csrc/conv_wgrad.hip) element by element, per geometry of their dispatch, against the float64
 operand rule of tests/conv_ref.py (reference semantics internal/nnet/forward.go:435-456 and
 internal/gpu/backward_ops.go:162-253).

@@ -1,4 +1,4 @@
-"""kf_gemm_fused on every tile of its dispatch (csrc/gemm.hip fused_impl), each with ragged
+"""kf_gemm_fused on every tile of its dispatch (csrc/gemm_fused.hip fused_impl), each with ragged
 tails, padded leading dimensions and every epilogue term, against the float64 rule of
 tests/gemm_ref.py (include/kf_ops.h KfEpilogue; reference semantics cpp/cuda/ops.cu:381-392 and
 internal/nnet/forward.go:589-695 for the terms the epilogue folds in).

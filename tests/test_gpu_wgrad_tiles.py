@@ -1,4 +1,4 @@
-"""kf_gemm_wgrad / kf_gemm_wgrad_scaled on every tile of their dispatch (csrc/gemm.hip
+"""kf_gemm_wgrad / kf_gemm_wgrad_scaled on every tile of their dispatch (csrc/gemm_wgrad.hip
 wgrad_impl), at a single split and at the default split-K target, against float64
 (tests/gemm_ref.py; reference semantics internal/gpu/backward_ops.go:162-253: dW = A^T B,
 db = column sums of B).
@@ -133,6 +133,39 @@ def test_wgrad_tile(gpu, case, target):
     assert np.array_equal(first[0].view(np.uint32), w2.view(np.uint32)), "dW differs between two runs"
     assert np.array_equal(first[1].view(np.uint32), bias2.view(np.uint32)), "db differs between two runs"
     for buf in keep + [dcs]:
+        buf.free()
+
+
+@pytest.mark.parametrize("with_bias", [False, True], ids=["dW", "dW+db"])
+def test_wgrad_reduce_timed_and_untimed(gpu, with_bias):
+    """The slab reduce runs one of two kernels (dW alone, or dW and the bias columns in one
+    launch), each on the plain or the timed launch path. On the smallest case, at the default
+    target (four splits): a profiled call leaves exactly one wgrad record (class 1) and one
+    reduce record (class 6), and its dW and db carry the bits of the unprofiled call."""
+    kf = gpu
+    c = min(CASES, key=lambda k: k["M"] * k["N"])
+    d = gr.wgrad_inputs(c)
+    a, b, keep = _operands(kf, c, d)
+    assert c["T"] >= 2 * 4 * 64   # one tile, at least 4 K-steps per split: at least two splits
+    old_target = kf.core.kf_gemm_wgrad_target(512)   # the default
+    try:
+        w, bias = _run(kf, c, d, a, b, None, 0, with_bias, False)
+        _check(c, d, w, bias, 0, False, c["id"])
+        try:
+            kf.core.kf_prof_reset()
+            kf.core.kf_prof_enable(1)
+            w2, bias2 = _run(kf, c, d, a, b, None, 0, with_bias, False)
+            classes = [r["cls"] for r in kf.prof_records()]
+        finally:
+            kf.core.kf_prof_reset()
+            kf.core.kf_prof_enable(0)
+    finally:
+        kf.core.kf_gemm_wgrad_target(old_target)
+    assert classes.count(1) == 1 and classes.count(6) == 1, classes
+    assert np.array_equal(w.view(np.uint32), w2.view(np.uint32)), "dW differs under profiling"
+    if with_bias:
+        assert np.array_equal(bias.view(np.uint32), bias2.view(np.uint32)), "db differs under profiling"
+    for buf in keep:
         buf.free()
 
 
