@@ -19,6 +19,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "kf_ops.h" /* KfNgOpts */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -158,6 +160,37 @@ int nnet_constrain_orthonormal(KfNet *net);
  * first n constrained components (n <= nnet_orthonormal_components; s = 0: the matrix was
  * all-zero or not finite and was left untouched). Any out pointer may be NULL. */
 int nnet_orthonormal_stats(KfNet *net, float *scale, float *ratio, float *err, int n);
+
+/* Natural-gradient preconditioning of the weight gradients (kf_ops.h kf_ng_*):
+ * Kaldi's NG-SGD, the online natural-gradient method of Povey, Zhang and Khudanpur. With the
+ * switch on, nnet_backward leaves in the gradient buffer, for every preconditioned component,
+ *   G^ = gamma_in gamma_out (I - W_in^T W_in) G (I - W_out^T W_out)
+ * instead of the plain G = X_ext^T dY (X_ext: the layer input as the weight gradient sees it, with
+ * the time splice and, for a component with a bias, an appended column of ones, so that G stacks
+ * dW over db), and advances the two preconditioners' states; nnet_sgd and nnet_update then see
+ * G^ with no change to either. Preconditioned: the update components of linear, output,
+ * tdnnf (.linear and .affine) and prefinal (.affine, .linear) layers on the output's path; conv,
+ * attention and per-sequence components keep plain gradients. opts: kf_ng_default_opts gives
+ * Kaldi's values (rank_in 20, rank_out 80, update_period 4, num_samples_history 2000, alpha 4).
+ * A side's rank is clamped to half its dimension (and to KF_NG_MAX_RANK); a side whose rank
+ * would be below 8 is left unpreconditioned. NULL turns the switch off: nnet_backward is then
+ * what it was, bit for bit. Setting it (again) allocates the state and scratch and starts every
+ * preconditioner from the default initial state; nothing is allocated per step. An error in
+ * MXFP8 mode, on a net bound to data parallel (and nnet_set_fp8 / nnet_bind_dp fail while it
+ * is on), with implicit dz, and in nnet_backward_n. */
+int nnet_set_natural_gradient(KfNet *net, const KfNgOpts *opts);
+/* the preconditioners (one per preconditioned side of a component), 0 when off */
+int nnet_natural_gradient_count(const KfNet *net);
+/* The report of the last nnet_backward (synchronises) for preconditioners 0 .. n-1: the update
+ * component (nnet_component_info index), the side (0 in, 1 out) and KF_NG_REPORT floats each:
+ * gamma, rho, sum(d), t (all before that step's state update), and a flag that is 1 when a
+ * non-finite statistic, eigenvalue or result made the update leave the state untouched. Any out
+ * pointer may be NULL. */
+int nnet_natural_gradient_stats(KfNet *net, int *component, int *side, float *report, int n);
+/* State read-back of preconditioner idx (synchronises), for tests and checkpoints: W [rank x dim]
+ * fp32, d [rank], rho, t. Any out pointer may be NULL (query dim and rank first). */
+int nnet_natural_gradient_state(KfNet *net, int idx, int *component, int *side, int *dim, int *rank, float *W,
+                                double *d, double *rho, double *t);
 
 /* MXFP8 train step (BASELINE configs[4]): 1 = every TDNN-F / linear / prefinal / output
  * GEMM whose input has an MXFP8 copy runs on the fp8 MFMA (kf_ops.h MXFP8 operands);

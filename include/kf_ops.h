@@ -312,6 +312,90 @@ typedef struct KfOrthoMat {
 long long kf_orthonormal_scratch_bytes(const KfOrthoMat *mats, int nmat);
 int kf_orthonormal_constrain(float *w32, void *w16, long long n_params, const KfOrthoMat *mats,
                              const KfOrthoMat *mats_dev, int nmat, void *scratch, float *stats);
+/* ---- Natural-gradient preconditioning (csrc/natgrad.hip) ----
+ * The online natural-gradient method of Povey, Zhang and Khudanpur (Kaldi's NG-SGD), batched
+ * over a table of preconditioners. A preconditioner works on row vectors of dimension D with
+ * rank R (8 <= R <= KF_NG_MAX_RANK, 2 R <= D); Rp = R rounded up to a multiple of 32. Its state:
+ *   w32 [Rp x D] fp32 at elements [w_off, w_off + Rp D) of the fp32 state buffer; rows R .. Rp-1
+ *       are zero (exact no-ops wherever W is used)
+ *   w16 the same matrix in fp16, the copy the statistics GEMMs read, at elements
+ *       [h_off, h_off + KF_NG_W16_HALFS(D, Rp)) of the fp16 state buffer: [Rp x ld] with
+ *       ld = KF_NG_W16_LD(D) (rows padded with zeros to a multiple of 8), then column D - 1 once
+ *       more as a contiguous [Rp] vector (the bias of H = X W^T when X ends in a column of ones)
+ *   sc  doubles at [s_off, s_off + 2 + Rp): rho, t (the step count), d[Rp] (d_i = 0 for i >= R)
+ * and its statistics of one minibatch X [N x D], fp32 at [st_off, st_off + KF_NG_STAT_FLOATS(D, Rp))
+ * of the statistics buffer (H = X W^T):
+ *   [0] trX = tr(X X^T), [1] N, [2 .. 31] unused
+ *   L  [Rp x Rp] = H^T H           at KF_NG_STAT_L
+ *   JT [D x Rp]  = X^T H = J^T     at KF_NG_STAT_JT(Rp)     (updating steps; K = J J^T is formed
+ *                                                            from it in double by the state kernel)
+ * With eta = min(0.9, 1 - exp(-N / num_samples_history)), beta = rho (1 + alpha) + alpha sum(d) / D,
+ * e_i = 1 / (beta / d_i + 1), f_i = e_i^-1/2, dr_i = d_i + rho:
+ *   gamma = sqrt(trX / (trX - sum_i (2 - e_i) L_ii))      (1 if either trace is 0 or not finite)
+ *   Z  = (eta/N)^2 F K F + (eta/N)(1 - eta)(Dr F L F + F L F Dr) + (1 - eta)^2 Dr^2
+ *   Z  = U diag(c) U^T, c descending; c_i = max(c_i, (rho (1 - eta))^2); s = sqrt(c)
+ *   rho' = max(epsilon, ((eta/N) trX + (1 - eta)(D rho + sum(d)) - sum(s)) / (D - R))
+ *   d'_i = max(s_i - rho', epsilon, delta max_j (s_j - rho'))
+ *   W' = E'^1/2 diag(1/s) U^T ((eta/N) F J + (1 - eta) Dr F W),  E' from d', rho'
+ * All of the state arithmetic runs in double; every sum has a fixed order, no atomics, no host
+ * round trip and no allocation, so two runs give the same bits.
+ * Tables: pres / comps in host memory (checked, size the launches) and the same tables in
+ * device memory (read by the kernels), uploaded once by the caller. */
+#define KF_NG_MAX_RANK 96
+#define KF_NG_STAT_L 32
+#define KF_NG_STAT_JT(Rp) (32 + (long long)(Rp) * (Rp))
+#define KF_NG_STAT_FLOATS(D, Rp) (32 + (long long)(Rp) * (Rp) + (long long)(D) * (Rp))
+#define KF_NG_W16_LD(D) (((D) + 7) / 8 * 8)
+#define KF_NG_W16_HALFS(D, Rp) ((long long)(Rp) * (KF_NG_W16_LD(D) + 1))
+#define KF_NG_REPORT 8 /* floats per preconditioner: gamma, rho, sum(d), t, flag, 0, 0, 0 */
+typedef struct KfNgOpts {
+    int rank_in, rank_out;     /* the network layer's ranks (kernels read the table's R): 20, 80 */
+    int update_period;         /* 4 */
+    float num_samples_history; /* 2000 */
+    float alpha;               /* 4 */
+    float epsilon, delta;      /* 1e-10, 5e-4 */
+} KfNgOpts;
+typedef struct KfNgPre {
+    int D, R;
+    long long w_off, h_off, s_off, st_off;
+} KfNgPre;
+/* a weight gradient G = [dW [K x N] at g + dw_off ; db [N] at g + db_off (db_off < 0: none)] with
+ * the preconditioners of its two sides (an index into pres, or -1: that side is left as it is):
+ * pres[pre_in].D == K + (db_off >= 0), pres[pre_out].D == N */
+typedef struct KfNgComp {
+    long long dw_off, db_off;
+    int K, N, pre_in, pre_out;
+} KfNgComp;
+void kf_ng_default_opts(KfNgOpts *opts);
+/* the default initial state: rho = d_i = epsilon, t = 0, R_0[i][j] = 1 / sqrt(ceil(D / R)) where
+ * j % R == i (rows re-normalised to unit length), W_0 = E^1/2 R_0 */
+int kf_ng_init(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, float *w32,
+               void *w16, double *sc);
+/* out[0] = sum of squares of the operand's elements (+ nrows with ones != 0: an appended column
+ * of ones), summed over the source rows with their multiplicities under the operand's splice
+ * (double, fixed order), rounded to fp32; out[1] = nrows: the head of a preconditioner's
+ * statistics. fp16 operands with hout = 1, no mask and no time stride. */
+int kf_ng_trx(const KfOperand *op, int ones, float *out);
+/* gamma of every preconditioner from trX, diag L and the state; writes report[KF_NG_REPORT p ..]
+ * = gamma, rho, sum(d), t, flag 0 */
+int kf_ng_scales(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, const double *sc,
+                 const float *stat, float *report);
+/* G <- gamma_in gamma_out (G - W_in^T (W_in G)), then G <- G - (G W_out^T) W_out, in place on
+ * every table entry, gamma from report (kf_ng_scales). Only the K N (+ N) elements of an entry
+ * are read or written. scratch: kf_ng_apply_scratch_bytes (16-byte aligned device memory) */
+long long kf_ng_apply_scratch_bytes(const KfNgComp *comps, int ncomp, const KfNgPre *pres, int npre);
+int kf_ng_apply(float *g, long long n_grad, const KfNgComp *comps, const KfNgComp *comps_dev, int ncomp,
+                const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const float *w32, const float *report,
+                void *scratch);
+/* one workgroup per preconditioner. update != 0: the state update above from L, JT, trX and N
+ * (Z built and diagonalised by cyclic Jacobi sweeps in double in LDS), w32 / w16 / d / rho
+ * replaced; a non-finite statistic, eigenvalue or result leaves them untouched and sets
+ * report[KF_NG_REPORT p + 4] = 1. Either way t <- t + 1.
+ * scratch: kf_ng_state_scratch_bytes (16-byte aligned device memory) */
+long long kf_ng_state_scratch_bytes(const KfNgPre *pres, int npre);
+int kf_ng_state(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, int update,
+                float *w32, void *w16, double *sc, const float *stat, void *scratch, float *report);
+
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.
  * Every source row must exist: 3(tc0-1) <= T-1 and, with a tail (tc > tc0), its lowest row

@@ -259,6 +259,12 @@ struct BackwardPass {
         return ok;
     }
 
+    // natural gradient: a component's statistics, issued where its weight gradient
+    // is, on the same stream and over the same operands
+    bool ng_stats(int pW, const KfOperand &X, const KfOperand &dY, int T);
+    bool ng_side(const KfNgPre &p, const KfOperand &X, bool ones, int T);
+    bool ng_finish();
+
     bool begin();
     int step(int li, int ndone);  // 1: go on below, 0: nothing trainable below, -1: failed
     bool finish();
@@ -275,7 +281,83 @@ struct BackwardPass {
     bool conv_dgrad_compact(Step &s), conv_dgrad_strided(Step &s), conv_dgrad_plain(Step &s);
 };
 
+// weak, as network.cpp's: a host layer linked against a backend without the kf_ng_* kernels
+// (the launch-trace stub) never gets past nnet_set_natural_gradient
+#pragma weak kf_ng_trx
+#pragma weak kf_ng_scales
+#pragma weak kf_ng_apply
+#pragma weak kf_ng_state
+
+// One side's statistics of a minibatch X [T x D] (kf_ops.h): trX and N, H = X W^T in fp16 (the
+// bias epilogue adds the ones column's term), L = H^T H, and on an updating step JT = X^T H
+// (its bias row: the ones column's). H is one buffer: the stream is in order.
+bool BackwardPass::ng_side(const KfNgPre &p, const KfOperand &X, bool ones, int T) {
+    const int Rp = (p.R + 31) / 32 * 32, K = X.ncols, ldh = KF_NG_W16_LD(p.D);
+    float *st = net->ng_stat + p.st_off;
+    const char *wh = (const char *)net->ng_w16 + p.h_off * 2;
+    if (X.mask || K + (ones ? 1 : 0) != p.D) {
+        set_err("natural gradient: a masked operand (implicit dz) or a shape that does not match the table");
+        return false;
+    }
+    if (!ck(kf_ng_trx(&X, ones ? 1 : 0, st), "natural gradient trX")) return false;
+    KfOperand Xk = X;
+    Xk.kcontig = 1;
+    KfOperand Wb = op_base(wh, ldh, Rp, K, 1);
+    KfEpilogue E = epi0();
+    E.out = net->ng_h;
+    E.ldo = Rp;
+    if (ones) E.bias = wh + (size_t)Rp * ldh * 2;
+    if (!ck(kf_gemm_fused(T, Rp, K, &Xk, &Wb, &E), "natural gradient H")) return false;
+    KfOperand H = op_base(net->ng_h, Rp, T, Rp, 0);
+    if (!ck(kf_gemm_wgrad(Rp, Rp, T, &H, &H, st + KF_NG_STAT_L, Rp, nullptr, 0), "natural gradient L")) return false;
+    if (!net->ng_updating) return true;
+    float *jt = st + KF_NG_STAT_JT(Rp);
+    return ck(kf_gemm_wgrad(K, Rp, T, &X, &H, jt, Rp, ones ? jt + (size_t)K * Rp : nullptr, 0), "natural gradient J");
+}
+
+bool BackwardPass::ng_stats(int pW, const KfOperand &X, const KfOperand &dY, int T) {
+    if (!net->ng_on || pW < 0 || net->ng_of_param[pW] < 0) return true;
+    const int ci = net->ng_of_param[pW];
+    const KfNgComp &c = net->ng_comps[ci];
+    if (c.pre_in >= 0 && !ng_side(net->ng_pres[c.pre_in], X, c.db_off >= 0, T)) return false;
+    if (c.pre_out >= 0 && !ng_side(net->ng_pres[c.pre_out], dY, false, T)) return false;
+    net->ng_issued[ci] = 1;
+    return true;
+}
+
+// after the weight-gradient stream is joined: the batched scales, apply and state launches
+bool BackwardPass::ng_finish() {
+    if (!net->ng_on || net->ng_comps.empty()) return true;
+    for (size_t i = 0; i < net->ng_comps.size(); ++i)
+        if (!net->ng_issued[i]) {
+            set_err("natural gradient: a preconditioned component got no weight gradient in this backward");
+            return false;
+        }
+    const KfNgPre *pres = net->ng_pres.data(), *pres_dev = (const KfNgPre *)net->ng_pres_dev;
+    const int npre = (int)net->ng_pres.size(), ncomp = (int)net->ng_comps.size();
+    if (!ck(kf_ng_scales(pres, pres_dev, npre, &net->ng_opts, net->ng_sc, net->ng_stat, net->ng_report), "natural gradient scales") ||
+        !ck(kf_ng_apply(net->grad, net->nparams, net->ng_comps.data(), (const KfNgComp *)net->ng_comps_dev, ncomp, pres,
+                        pres_dev, npre, net->ng_w32, net->ng_report, net->ng_apply_scratch),
+            "natural gradient apply") ||
+        !ck(kf_ng_state(pres, pres_dev, npre, &net->ng_opts, net->ng_updating ? 1 : 0, net->ng_w32, net->ng_w16, net->ng_sc,
+                        net->ng_stat, net->ng_state_scratch, net->ng_report),
+            "natural gradient state"))
+        return false;
+    ++net->ng_t;
+    net->ng_ran = true;
+    return true;
+}
+
 bool BackwardPass::begin() {
+    if (net->ng_on) {
+        if (net->implicit_dz || net->fp8 || net->dp || (two && net->main_aff > 0)) {
+            set_err("natural gradient: not supported with implicit dz, MXFP8, data parallel or nnet_debug_backward's "
+                    "main_aff");
+            return false;
+        }
+        std::fill(net->ng_issued.begin(), net->ng_issued.end(), 0);
+        net->ng_updating = net->ng_t < 10 || net->ng_t % net->ng_opts.update_period == 0;
+    }
     if (hp) {
         if (kf_event_record(net->ev_go, caller) != 0 || kf_stream_wait(net->hp_stream, net->ev_go) != 0) {
             set_err("backward: chain stream order");
@@ -404,7 +486,7 @@ bool BackwardPass::finish() {
         set_err(std::string("dp join: ") + (kf_dp_last_error() ? kf_dp_last_error() : ""));
         return false;
     }
-    return true;
+    return ng_finish();
 }
 
 // the first compact layer's input gradient goes to the compact rows (net->dzc), through the
@@ -441,7 +523,10 @@ bool BackwardPass::linear(Step &s) {
     const int T = s.T, din = nl.L.in_dim, dout = nl.L.out_dim;
     KfOperand A = op_base(s.x, din, T, din, 0);
     KfOperand B = op_base(dz, dout, T, dout, 0);
-    if (!wgrad([&] { return ck(kf_gemm_wgrad(din, dout, T, &A, &B, gptr(net, nl.pW), dout, gptr(net, nl.pb), 0), "wgrad"); }))
+    if (!wgrad([&] {
+            return ck(kf_gemm_wgrad(din, dout, T, &A, &B, gptr(net, nl.pW), dout, gptr(net, nl.pb), 0), "wgrad") &&
+                   ng_stats(nl.pW, A, B, T);
+        }))
         return false;
     if (!s.want_dx) return true;
     KfOperand A2 = op_base(dz, dout, T, dout, 1);
@@ -475,7 +560,8 @@ bool BackwardPass::prefinal(Step &s) {
     KfOperand A = op_base(nl.aux, big, T, big, 0);
     KfOperand B = op_base(dz, small, T, small, 0);
     if (!wgrad([&] {
-            return ck(kf_gemm_wgrad(big, small, T, &A, &B, gptr(net, nl.pW2), small, nullptr, 0), "prefinal small wgrad");
+            return ck(kf_gemm_wgrad(big, small, T, &A, &B, gptr(net, nl.pW2), small, nullptr, 0), "prefinal small wgrad") &&
+                   ng_stats(nl.pW2, A, B, T);
         }))
         return false;
     void *dzbig = s.dbott_buf;
@@ -492,7 +578,8 @@ bool BackwardPass::prefinal(Step &s) {
     KfOperand A3 = op_base(s.x, din, T, din, 0);
     KfOperand B3 = op_base(dzbig, big, T, big, 0);
     if (!wgrad([&] {
-            return ck(kf_gemm_wgrad(din, big, T, &A3, &B3, gptr(net, nl.pW), big, gptr(net, nl.pb), 0), "prefinal big wgrad");
+            return ck(kf_gemm_wgrad(din, big, T, &A3, &B3, gptr(net, nl.pW), big, gptr(net, nl.pb), 0), "prefinal big wgrad") &&
+                   ng_stats(nl.pW, A3, B3, T);
         }))
         return false;
     if (!s.want_dx) return true;
@@ -594,7 +681,8 @@ bool BackwardPass::tdnnf_affine_wgrad(Step &s, const Tdnnf &t) {
     if (t.imp)
         return ck(kf_gemm_wgrad_scaled(t.kaff, dout, T, &A, &B, gptr(net, nl.pW2), dout, gptr(net, nl.pb2), 0, nl.bn_scale),
                   "tdnnf affine wgrad");
-    return ck(kf_gemm_wgrad(t.kaff, dout, T, &A, &B, gptr(net, nl.pW2), dout, gptr(net, nl.pb2), 0), "tdnnf affine wgrad");
+    return ck(kf_gemm_wgrad(t.kaff, dout, T, &A, &B, gptr(net, nl.pW2), dout, gptr(net, nl.pb2), 0), "tdnnf affine wgrad") &&
+           ng_stats(nl.pW2, A, B, T);
 }
 
 // bottleneck gradient: transpose of the [0, +s] clamped splice
@@ -684,7 +772,8 @@ bool BackwardPass::tdnnf_linear_wgrad(Step &s, const Tdnnf &t) {
     const int T = s.T, din = s.nl.L.in_dim;
     KfOperand A2 = t.s > 0 ? op_splice(s.x, T, din, -t.s, 0, KF_CLAMP, 0) : op_base(s.x, din, T, din, 0);
     KfOperand B2 = op_base(t.dbott, t.bn, T, t.bn, 0);
-    return ck(kf_gemm_wgrad(t.klin, t.bn, T, &A2, &B2, gptr(net, s.nl.pW), t.bn, nullptr, 0), "tdnnf linear wgrad");
+    return ck(kf_gemm_wgrad(t.klin, t.bn, T, &A2, &B2, gptr(net, s.nl.pW), t.bn, nullptr, 0), "tdnnf linear wgrad") &&
+           ng_stats(s.nl.pW, A2, B2, T);
 }
 
 // input gradient: transpose of the [-s, 0] clamped splice
@@ -956,7 +1045,13 @@ extern "C" int nnet_backward(KfNet *net, const void *out_grad) {
     return backward_impl(net, out_grad, 1 << 30);
 }
 // debugging / tests: back-propagate through the top `n` layers only
-extern "C" int nnet_backward_n(KfNet *net, const void *out_grad, int n) { return backward_impl(net, out_grad, n); }
+extern "C" int nnet_backward_n(KfNet *net, const void *out_grad, int n) {
+    if (net && net->ng_on) {
+        set_err("backward_n: not supported with natural gradient on");
+        return -1;
+    }
+    return backward_impl(net, out_grad, n);
+}
 // debugging / tests: device pointers of internal tensors
 extern "C" const void *nnet_debug_tensor(KfNet *net, const char *what, int layer) {
     std::string w = what;

@@ -211,6 +211,23 @@ struct KfNet {
     size_t ort_cap = 0;         // entries ort_mats_dev / ort_stats hold
     long long ort_scratch_bytes = 0;
     bool ort_ran = false;  // ort_stats holds a call's report
+    // natural-gradient preconditioning (kf_nnet.h nnet_set_natural_gradient): the preconditioner
+    // and component tables on the host and on the device (kf_ops.h KfNgPre / KfNgComp), state,
+    // statistics, scratch and report, all made when the switch is set
+    bool ng_on = false;
+    KfNgOpts ng_opts{};
+    std::vector<KfNgPre> ng_pres;
+    std::vector<KfNgComp> ng_comps;
+    std::vector<int> ng_pre_comp, ng_pre_side;  // per preconditioner: update component, 0 in / 1 out
+    std::vector<int> ng_of_param;               // weight tensor -> its entry of ng_comps, or -1
+    std::vector<char> ng_issued;                // per entry: this backward issued its statistics
+    void *ng_pres_dev = nullptr, *ng_comps_dev = nullptr, *ng_w16 = nullptr, *ng_h = nullptr;
+    void *ng_apply_scratch = nullptr, *ng_state_scratch = nullptr;
+    float *ng_w32 = nullptr, *ng_stat = nullptr, *ng_report = nullptr;
+    double *ng_sc = nullptr;
+    long long ng_t = 0;      // steps so far: t < 10 or t % update_period == 0 updates the state
+    bool ng_updating = false;  // this backward's steps
+    bool ng_ran = false;     // ng_report holds a backward's report
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]

@@ -151,6 +151,10 @@ _sig(nnet, "nnet_set_component_orthonormal", _i, _vp, C.c_char_p, _f)
 _sig(nnet, "nnet_orthonormal_components", _i, _vp, C.POINTER(_i), _i)
 _sig(nnet, "nnet_constrain_orthonormal", _i, _vp)
 _sig(nnet, "nnet_orthonormal_stats", _i, _vp, _vp, _vp, _vp, _i)
+_sig(nnet, "nnet_set_natural_gradient", _i, _vp, _vp)
+_sig(nnet, "nnet_natural_gradient_count", _i, _vp)
+_sig(nnet, "nnet_natural_gradient_stats", _i, _vp, _vp, _vp, _vp, _i)
+_sig(nnet, "nnet_natural_gradient_state", _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig(nnet, "nnet_bind_grad_buffer", _i, _vp, _vp)
 _sig(nnet, "nnet_backward_n", _i, _vp, _vp, _i)
 _sig(nnet, "nnet_debug_tensor", _vp, _vp, C.c_char_p, _i)
@@ -525,6 +529,53 @@ class Network:
               "nnet_orthonormal_stats")
         return dict(names=names, scale=s, ratio=r, err=e)
 
+    # Natural-gradient preconditioning (kf_nnet.h nnet_set_natural_gradient) ----
+    def set_natural_gradient(self, on: bool = True, **opts):
+        """Kaldi's NG-SGD on the weight gradients of the linear, output, tdnnf and prefinal
+        components: backward() then leaves the preconditioned gradient for sgd() / update().
+        opts override kf_ng_default_opts (rank_in 20, rank_out 80, update_period 4,
+        num_samples_history 2000, alpha 4); every call with on=True starts the preconditioners
+        from their default initial state. on=False: the plain gradients, as before."""
+        if not on:
+            check(nnet.nnet_set_natural_gradient(self.h, None), "nnet_set_natural_gradient")
+            return
+        o = KfNgOpts()
+        core.kf_ng_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in dict(KfNgOpts._fields_):
+                raise TypeError(f"set_natural_gradient: unknown option {k}")
+            setattr(o, k, v)
+        check(nnet.nnet_set_natural_gradient(self.h, C.byref(o)), "nnet_set_natural_gradient")
+
+    def natural_gradient_stats(self) -> list:
+        """The last backward's report (synchronises), one dict per preconditioned side of a
+        component: name, side ("in" / "out"), gamma, rho, sum_d, t (all before that step's
+        state update) and flag (True: a non-finite statistic left the state untouched)."""
+        n = nnet.nnet_natural_gradient_count(self.h)
+        comp, side = (_i * max(n, 1))(), (_i * max(n, 1))()
+        rep = np.zeros((max(n, 1), NG_REPORT), np.float32)
+        check(nnet.nnet_natural_gradient_stats(self.h, comp, side, rep.ctypes.data, n), "nnet_natural_gradient_stats")
+        names = [c["name"] for c in self.components()]
+        return [dict(name=names[comp[i]], side="out" if side[i] else "in", gamma=float(rep[i, 0]), rho=float(rep[i, 1]),
+                     sum_d=float(rep[i, 2]), t=int(rep[i, 3]), flag=bool(rep[i, 4])) for i in range(n)]
+
+    def natural_gradient_state(self) -> list:
+        """The preconditioners' states (synchronises), in natural_gradient_stats() order: name,
+        side, W [rank x dim] float32, d [rank] and rho (float64), t."""
+        names = [c["name"] for c in self.components()]
+        out = []
+        for i in range(nnet.nnet_natural_gradient_count(self.h)):
+            comp, side, dim, rank = _i(), _i(), _i(), _i()
+            check(nnet.nnet_natural_gradient_state(self.h, i, C.byref(comp), C.byref(side), C.byref(dim), C.byref(rank),
+                                                   None, None, None, None), "nnet_natural_gradient_state")
+            W, d = np.empty((rank.value, dim.value), np.float32), np.empty(rank.value, np.float64)
+            rho, t = C.c_double(), C.c_double()
+            check(nnet.nnet_natural_gradient_state(self.h, i, None, None, None, None, W.ctypes.data, d.ctypes.data,
+                                                   C.byref(rho), C.byref(t)), "nnet_natural_gradient_state")
+            out.append(dict(name=names[comp.value], side="out" if side.value else "in", W=W, d=d, rho=rho.value,
+                            t=int(t.value)))
+        return out
+
     def dp_plan(self, bucket_bytes: int, max_buckets: int = 256):
         """[(after_step, begin, end)]: the gradient buckets nnet_backward exchanges
         (kf_nnet.h nnet_dp_plan), in issue order."""
@@ -698,6 +749,49 @@ class KfOrthoMat(C.Structure):
 
 _sig(core, "kf_orthonormal_scratch_bytes", _ll, _vp, _i)
 _sig(core, "kf_orthonormal_constrain", _i, _vp, _vp, _ll, _vp, _vp, _i, _vp, _vp)
+
+
+# natural-gradient preconditioning (kf_ops.h kf_ng_*, csrc/natgrad.hip)
+class KfNgOpts(C.Structure):
+    _fields_ = [("rank_in", _i), ("rank_out", _i), ("update_period", _i), ("num_samples_history", _f),
+                ("alpha", _f), ("epsilon", _f), ("delta", _f)]
+
+
+class KfNgPre(C.Structure):
+    _fields_ = [("D", _i), ("R", _i), ("w_off", _ll), ("h_off", _ll), ("s_off", _ll), ("st_off", _ll)]
+
+
+class KfNgComp(C.Structure):
+    _fields_ = [("dw_off", _ll), ("db_off", _ll), ("K", _i), ("N", _i), ("pre_in", _i), ("pre_out", _i)]
+
+
+NG_MAX_RANK, NG_REPORT = 96, 8  # kf_ops.h KF_NG_MAX_RANK, KF_NG_REPORT
+
+
+def ng_rp(R: int) -> int:
+    """a rank as it is stored: padded with zero rows to a multiple of 32"""
+    return (R + 31) // 32 * 32
+
+
+def ng_w16_ld(D: int) -> int:
+    """kf_ops.h KF_NG_W16_LD: the row pitch of a preconditioner's fp16 copy"""
+    return (D + 7) // 8 * 8
+
+
+def ng_stat_offsets(D: int, R: int) -> dict:
+    """kf_ops.h KF_NG_STAT_*: where L and JT lie in a preconditioner's statistics, and their size"""
+    Rp = ng_rp(R)
+    return dict(L=32, JT=32 + Rp * Rp, floats=32 + Rp * Rp + D * Rp)
+
+
+_sig(core, "kf_ng_default_opts", None, C.POINTER(KfNgOpts))
+_sig(core, "kf_ng_init", _i, _vp, _vp, _i, C.POINTER(KfNgOpts), _vp, _vp, _vp)
+_sig(core, "kf_ng_trx", _i, C.POINTER(KfOperand), _i, _vp)
+_sig(core, "kf_ng_scales", _i, _vp, _vp, _i, C.POINTER(KfNgOpts), _vp, _vp, _vp)
+_sig(core, "kf_ng_apply_scratch_bytes", _ll, _vp, _i, _vp, _i)
+_sig(core, "kf_ng_apply", _i, _vp, _ll, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp)
+_sig(core, "kf_ng_state_scratch_bytes", _ll, _vp, _i)
+_sig(core, "kf_ng_state", _i, _vp, _vp, _i, C.POINTER(KfNgOpts), _i, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows_from", _i, _vp, _vp, _ll, _i, _i, _i, _i)

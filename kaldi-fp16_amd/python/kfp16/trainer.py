@@ -10,6 +10,8 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
   4. optimizer.Update per tensor  -> Network.sgd over the flat buffer (optimize.go:95-142),
                                      or with TrainConfig.kaldi_update Network.update: Kaldi's
                                      per-component max-change, L2 and learning-rate factors
+  3a. (TrainConfig.natural_gradient) -> Network.set_natural_gradient: Kaldi's NG-SGD, the weight
+                                     gradients preconditioned inside Network.backward
   5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
                                      ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
@@ -53,6 +55,10 @@ class TrainConfig:
     # update; Kaldi handles each component at one update in four on average, which is N = 4.
     # 0: never, as before.
     orthonormal_every: int = 0
+    # natural_gradient: Kaldi's NG-SGD (Network.set_natural_gradient with its default options):
+    # the backward leaves the preconditioned weight gradients of the linear, output, tdnnf and
+    # prefinal components for step 4, with either update. False: plain gradients, as before.
+    natural_gradient: bool = False
 
 
 def chain_rows(frame_offsets, num_frames, frames_per_seq, subsampling: int, left_context: int):
@@ -91,6 +97,8 @@ class EgsTrainer:
         self.ivec = DeviceBuffer(max_egs * self.ivec_dim * 2) if self.ivec_dim else None
         self.max_egs = max_egs
         self.steps = 0  # steps taken
+        if self.cfg.natural_gradient:
+            self.net.set_natural_gradient(True)
 
     def step(self, batch, allreduce=None):
         """One TrainStep on `batch` (kfp16.egs.TrainingBatch). allreduce: optional callable
