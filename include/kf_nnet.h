@@ -192,6 +192,47 @@ int nnet_natural_gradient_stats(KfNet *net, int *component, int *side, float *re
 int nnet_natural_gradient_state(KfNet *net, int idx, int *component, int *side, int *dim, int *rank, float *W,
                                 double *d, double *rho, double *t);
 
+/* Per-sequence dropout of the TDNN-F layers (kf_ops.h kf_dropout_masks): Kaldi's
+ * tdnnf-layer is linear -> affine -> ReLU -> BatchNorm -> dropout -> + bypass-scale * input,
+ * the dropout a GeneralDropoutComponent with continuous=true, time-period=0, block-dim=dim: one
+ * factor m = (1 - 2p) + 4p u, u ~ U[0, 1), per (sequence, column), shared by all frames of the
+ * sequence, mean 1, no rescaling; the bypass does not go through it. A tdnnf-layer has the
+ * component when its xconfig line carries dropout-proportion >= 0 (the key's default, -1,
+ * means none; allowed: -1 or [0, 0.5]). With the switch on, the affine GEMM's epilogue applies
+ *   y = rne((relu(z) scale + shift) m[b][n] + bypass x)
+ * and the input-gradient GEMM that produces the layer's dz writes
+ *   dz = rne(v bnscale[n] m[b][n] relu_bit)
+ * so weight gradients, bottleneck gradients and NG-SGD need no change. Every call below but
+ * nnet_dropout_mask works on a layout-only net.
+ *
+ * nnet_set_sequences: the sequence boundaries of later nnet_forward calls with
+ * T == seq_row0[B] (seq_row0 host int[B + 1], seq_row0[0] = 0, strictly increasing, as
+ * nnet_forward_ivector's, which sets them itself); NULL, 0 or no call: the whole input is one
+ * sequence. With dropout on, a forward whose T differs from the boundaries given fails. */
+int nnet_set_sequences(KfNet *net, const int *seq_row0, int B);
+/* the layers with a dropout component (nnet_layer_info indices): returns their number and
+ * writes the first n to idx (may be NULL) */
+int nnet_dropout_layers(const KfNet *net, int *idx, int n);
+/* Kaldi's set-dropout-proportion: 0 <= p <= 0.5 on the named layer, or with layer = NULL on
+ * every layer with a component. A named layer without a component is an error. */
+int nnet_set_dropout_proportion(KfNet *net, const char *layer, float p);
+/* a layer's current proportion, -1 when it has no component */
+int nnet_dropout_proportion(const KfNet *net, const char *layer, float *p);
+/* The switch (default off: test mode) and the generator's 64-bit seed. Off, or every
+ * proportion 0, leaves forward and backward what they were, bit for bit. While on, each
+ * forward draws the masks of (seed, step) for every layer with p > 0 (one launch) and the step
+ * then advances by one, masks drawn or not; the backward uses the masks of its forward. The
+ * mask tables grow with the largest number of sequences seen; nothing is allocated per step.
+ * On a net with a dropout component: an error in MXFP8 mode and with implicit dz, and while
+ * on, nnet_set_fp8, nnet_set_implicit_dz and nnet_backward_n fail. The step is not reset. */
+int nnet_set_dropout(KfNet *net, int on, unsigned long long seed);
+/* the step the next forward draws with (0 <= step < 2^32; it wraps there): replay */
+int nnet_set_dropout_step(KfNet *net, long long step);
+long long nnet_dropout_step(const KfNet *net);
+/* the mask the last forward drew for a layer (synchronises): host fp32 [B x dim] (NULL: only
+ * B and dim). An error when that forward drew none for it (dropout off, p = 0). */
+int nnet_dropout_mask(KfNet *net, const char *layer, float *host, int *B, int *dim);
+
 /* MXFP8 train step (BASELINE configs[4]): 1 = every TDNN-F / linear / prefinal / output
  * GEMM whose input has an MXFP8 copy runs on the fp8 MFMA (kf_ops.h MXFP8 operands);
  * the producing epilogues write those copies, weights are re-quantised on every

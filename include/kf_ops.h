@@ -92,9 +92,11 @@ typedef struct {
  *   v = alpha*acc (+ beta*out[m][n]) (+ bias[n])
  *   if relu: mask_out bit (m*ldo+n) = v > 0; v = max(v, 0)
  *   if scale: v = v*scale[n] + shift[n]          (frozen BatchNorm, folded)
+ *   if drop and scale: v *= drop[row_seg[m]][n]   (per-sequence dropout mask, below)
  *   if resid: v += resid_alpha * resid[m][n]     (TDNN-F bypass / grad bypass)
  *   out[m][n] = rne_fp16(v)                       (when out != NULL)
- *   if out2: out2[m][n] = rne_fp16(v * scale2[n] * bit(mask_in, m*ldo2+n))
+ *   if out2: out2[m][n] = rne_fp16(v * scale2[n] * bit(mask_in, m*ldo2+n)), with drop and
+ *            out2: rne_fp16((v * scale2[n]) * drop[row_seg[m]][n] * bit(mask_in, m*ldo2+n))
  *   if out8: MXFP8 copy (kf_quant_mxfp8's rule, 32-column blocks) of the unrounded v, or
  *            with out8_src = 1 of the unrounded out2 value
  *   if edge_out: edge_out[n] = rne_fp16(sum over rows m in [edge_r0, edge_r1) of the stored
@@ -103,6 +105,14 @@ typedef struct {
  *            separate sum kernel after the GEMM when the rows span two tiles)
  * Masks are bit-packed in the linear element order of the tensor they describe
  * (bit i of byte i/8), so producer and consumer may tile differently.
+ * drop: a column factor per row segment, Kaldi's GeneralDropoutComponent with
+ * one mask row per sequence: fp32 [nseg x ld_drop], row_seg[m] the segment of GEMM row m. A
+ * launch uses it for one of the two places above, never both: with scale (the forward, after
+ * the BatchNorm step and before the bypass) or with out2 (the input gradient's dz). drop with
+ * neither or with both, without row_seg, with row_group, out8, beta != 0, a masked or an MXFP8 operand,
+ * ld_drop % 8 != 0 or a drop pointer that is not 16-byte aligned fails; so does a product
+ * that would run on a tile without the drop variant (it exists for N > 64 other than
+ * N = 160 / 320 with a plain or two-part time-spliced A and B, fp16).
  */
 typedef struct {
     void *out;
@@ -131,6 +141,9 @@ typedef struct {
      * resid, mask_out, mask_in, out8): a transposed conv evaluated on every third frame
      * writes its frames in place. 0 = rows as they are. Not with edge_out. */
     int row_group, row_stride;
+    const float *drop;      /* fp32 [nseg x ld_drop] per-segment column factors, or NULL */
+    long long ld_drop;
+    const int32_t *row_seg; /* [M]: the segment (row of drop) of GEMM row m; required with drop */
 } KfEpilogue;
 
 /* current stream for every launch made by this library on the calling thread
@@ -395,6 +408,32 @@ int kf_ng_apply(float *g, long long n_grad, const KfNgComp *comps, const KfNgCom
 long long kf_ng_state_scratch_bytes(const KfNgPre *pres, int npre);
 int kf_ng_state(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, int update,
                 float *w32, void *w16, double *sc, const float *stat, void *scratch, float *report);
+
+/* ---- Per-sequence dropout masks (csrc/dropout.hip) ----
+ * Kaldi's GeneralDropoutComponent with continuous = true, time-period = 0, block-dim = dim: one
+ * factor per (sequence b, column n), shared by every frame of the sequence and applied by the
+ * fused GEMM epilogue (KfEpilogue.drop above):
+ *   x = Philox4x32-10(counter = {step, ordinal, b, n / 4}, key = {seed low, seed high})[n % 4]
+ *   u = (x >> 8) * 2^-24,  mask[b * ld + n] = fmaf(4 p, u, 1 - 2 p)        (fp32)
+ * uniform on [1 - 2p, 1 + 2p) with mean 1. Stateless: the same (seed, step, ordinal) gives the
+ * same mask, in one launch for all n layers (per KF_DROP_MAX of them); an entry with p = 0 is
+ * skipped (nothing is written). 0 <= p <= 0.5, dim % 4 == 0, ld % 4 == 0, ld >= dim, 16-byte
+ * aligned mask, 0 <= step < 2^32, B <= 65535. `layers` is a host array. */
+#define KF_DROP_MAX 32
+typedef struct KfDropLayer {
+    float *mask;   /* device fp32 [B x ld] */
+    long long ld;
+    int dim;
+    int ordinal;   /* the layer's place in the counter */
+    float p;
+    int reserved;  /* 0 */
+} KfDropLayer;
+int kf_dropout_masks(int n, const KfDropLayer *layers, int B, unsigned long long seed, long long step);
+/* row_seg[r] = the sequence of GEMM row r (KfEpilogue.row_seg), from the device sequence offsets
+ * dev_seq_off int[B + 1] (seq_off[0] = 0, seq_off[B] = T; B <= 1: one sequence, all zeros).
+ * tc = 0: rows are the T frames. tc > 0: rows are the tc compact rows of the row-subsampled
+ * step (the rule and its conditions as kf_gather_rows below). */
+int kf_row_seg(int32_t *row_seg, const int *dev_seq_off, int B, int T, int tc0, int tc);
 
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.

@@ -139,6 +139,9 @@ __device__ __forceinline__ half8 load_frag(const char *tile, int idx0, int s, in
 enum { OP_SIMPLE = 0, OP_P2 = 1, OP_GEN = 2 };
 // or-ed into a gemm_kernel operand mode: the operand is masked (Stager MK)
 constexpr int OP_MASKED = 8;
+// or-ed into gemm_kernel's A operand mode (the operand that names the output rows): the fused
+// epilogue applies KfEpilogue.drop per row segment (fused_epilogue's DR variant)
+constexpr int EPI_DROP = 16;
 constexpr unsigned BAD = 0xFFFFFFFFu;  // byte offset that reads as zero (buffer range check)
 
 // buffer resource (SGPR quad): base, stride 0, 2^32 - 1 records (an offset of BAD reads
@@ -435,14 +438,24 @@ struct EpiCols {
     const float *bias, *scale, *shift, *scale2;  // LDS, indexed by local column
 };
 
+// DR: the launch carries KfEpilogue.drop; dr holds the 8 factors of this row's segment
+// (drop[row_seg[m]][n .. n + 7], loaded a chunk ahead: fused_epilogue). They scale the
+// BatchNorm output when the launch has one (the forward), else out2's value (the input
+// gradient's dz); the host admits no launch with both.
+struct Drop8 {
+    float4v lo, hi;
+};
+template <bool DR = false>
 __device__ __forceinline__ void epilogue8(const KfEpilogue &E, const EpiCols &P, long long m, int n,
                                           int nl, float v[8], half8 cold, half8 rres,
-                                          unsigned mbits) {
+                                          unsigned mbits, const Drop8 *dr = nullptr) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] *= E.alpha;
-    if (E.beta != 0.f) {
+    if constexpr (!DR) {  // (the drop variant takes no old-C operand: host-checked)
+        if (E.beta != 0.f) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += E.beta * (float)cold[e];
+            for (int e = 0; e < 8; ++e) v[e] += E.beta * (float)cold[e];
+        }
     }
     if (E.bias) {
 #pragma unroll
@@ -460,6 +473,13 @@ __device__ __forceinline__ void epilogue8(const KfEpilogue &E, const EpiCols &P,
     if (E.scale) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = fmaf(v[e], P.scale[nl + e], P.shift[nl + e]);
+        if constexpr (DR) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] *= dr->lo[e];
+                v[e + 4] *= dr->hi[e];
+            }
+        }
     }
     if (E.resid) {
 #pragma unroll
@@ -477,6 +497,9 @@ __device__ __forceinline__ void epilogue8(const KfEpilogue &E, const EpiCols &P,
         for (int e = 0; e < 8; ++e) {
             float w = v[e];
             if (E.scale2) w *= P.scale2[nl + e];
+            if constexpr (DR) {
+                if (!E.scale) w *= e < 4 ? dr->lo[e & 3] : dr->hi[e & 3];
+            }
             if (E.mask_in && !((mbits >> e) & 1u)) w = 0.f;
             o[e] = f2h(w);
             if (E.out8_src) v[e] = w;  // the MXFP8 copy after this call quantises out2's value

@@ -82,6 +82,23 @@ static int fused_impl(int M, int N, int K, const KfOperand *A, const KfOperand *
         kf_report_error("kf_gemm_fused: grouped output rows (row_group) need an fp16 conv input gradient");
         return -1;
     }
+    if (E.drop) {
+        // the forward scales the BatchNorm output, the input gradient out2's value: exactly one
+        if (!E.row_seg || (E.scale != nullptr) == (E.out2 != nullptr)) {
+            kf_report_error("kf_gemm_fused: drop needs row_seg and exactly one of scale (forward) and out2 (input "
+                            "gradient)");
+            return -1;
+        }
+        if (E.row_group || E.out8 || E.beta != 0.f || f8 || a.mk || b.mk || edge || am == OP_GEN || bm == OP_GEN) {
+            kf_report_error("kf_gemm_fused: drop does not go with row_group, out8, beta, MXFP8, masked or conv operands");
+            return -1;
+        }
+        if (E.ld_drop < N || E.ld_drop % 8 || ((uintptr_t)E.drop & 15) || ((uintptr_t)E.row_seg & 3)) {
+            kf_report_error("kf_gemm_fused: drop needs ld_drop >= N, ld_drop %% 8 == 0 and a 16-byte aligned table "
+                            "(ld_drop=%lld N=%d)", E.ld_drop, N);
+            return -1;
+        }
+    }
     if (f8) {
         if (K % 128 || am == OP_GEN || a.edges || bm != OP_SIMPLE) {
             kf_report_error("kf_gemm_fused: MXFP8 needs K %% 128 == 0, a plain or time-spliced A and a "
@@ -122,7 +139,7 @@ static int fused_impl(int M, int N, int K, const KfOperand *A, const KfOperand *
                         "k-contiguous B of the same kind, no MXFP8 copy) (M=%d N=%d K=%d)", M, N, K);
         return -1;
     }
-    {  // the halo kernel shares fused_epilogue, MXFP8 copy included (BN >= 64)
+    if (!E.drop) {  // the halo kernel shares fused_epilogue, MXFP8 copy included (BN >= 64)
         const int hr = conv_halo_try(M, N, K, a, b, bm, B->kcontig != 0, E);
         if (hr != 0) return hr < 0 ? -1 : 0;
     }
@@ -151,6 +168,13 @@ static int fused_impl(int M, int N, int K, const KfOperand *A, const KfOperand *
     if (tile == 5 && (long long)((M + 383) / 384) * ((N + 159) / 160) < 192) tile = 8;
     // (64x160 tiles instead measured 25.21 against 25.05 ms, same box: not used)
     if (!B->kcontig) return fused_mn(tile, am, bm, M, N, K, a, b, E, G);
+    if (E.drop) {  // am, bm are plain or two-part here (checked above)
+        if (am == OP_SIMPLE && bm == OP_SIMPLE) return fused_tile_drop<true, OP_SIMPLE, OP_SIMPLE>(tile, M, N, K, a, b, E, G);
+        if (am == OP_P2 && bm == OP_SIMPLE) return fused_tile_drop<true, OP_P2, OP_SIMPLE>(tile, M, N, K, a, b, E, G);
+        if (am == OP_P2 && bm == OP_P2) return fused_tile_drop<true, OP_P2, OP_P2>(tile, M, N, K, a, b, E, G);
+        kf_report_error("kf_gemm_fused: drop with a plain A needs a plain B (M=%d N=%d K=%d)", M, N, K);
+        return -1;
+    }
     if (am == OP_SIMPLE && bm == OP_SIMPLE) return fused_tile<true, OP_SIMPLE, OP_SIMPLE>(tile, M, N, K, a, b, E, G);
     if (am == OP_P2 && bm == OP_SIMPLE) return fused_tile<true, OP_P2, OP_SIMPLE>(tile, M, N, K, a, b, E, G);
     if (am == OP_P2 && bm == OP_P2) return fused_tile<true, OP_P2, OP_P2>(tile, M, N, K, a, b, E, G);

@@ -197,10 +197,23 @@ struct EpiMap {
 
 // RG: the epilogue honours KfEpilogue.row_group (the conv input-gradient halo kernels only:
 // the row map's registers cost the 80 KB GEMM tiles their second workgroup per CU)
-template <int BM, int BN, int WM, int WN, bool RG = false>
+// DR: the epilogue applies KfEpilogue.drop (the per-sequence dropout factor, kf_ops.h): a
+// compile-time variant, so that every launch without drop keeps the code it had. The tile's
+// row -> segment map (rsg: row_seg[m0 + tid], loaded before the K loop like the column
+// parameters) goes to LDS behind them, `smem` then holding BM more dwords. The 8 factors of an
+// item (two 16-byte loads from a table that lives in L2) sit in ONE register slot per item: a
+// second slot, filled with the other row operands a chunk ahead, is 8 * ITEMS more registers
+// and costs the 80 KB tiles their second workgroup per CU (128x192: 126 -> 172 VGPRs). So chunk
+// 0's factors are issued with the first prefetch, before any store, and item k of chunk
+// ic + 1 is issued right after item k of chunk ic has used the slot: a chunk ahead of its use,
+// behind that item's own stores only, so its wait never queues behind stores that are still
+// in flight when it is needed. The variant takes no beta (old C) operand (host-checked): its
+// registers pay for the slot. DESIGN.md §21 lists what each tile uses.
+template <int BM, int BN, int WM, int WN, bool RG = false, bool DR = false>
 __device__ __forceinline__ void fused_epilogue(float4v (&acc)[BM / WM / 16][BN / WN / 16], char *smem,
                                                const KfEpilogue &E, int M, int N, int m0, int n0,
-                                               int tid, int lane, int wave, const EpiPre *pre = nullptr) {
+                                               int tid, int lane, int wave, const EpiPre *pre = nullptr,
+                                               int rsg = 0) {
     constexpr int NW = WM * WN, NTH = 64 * NW;
     constexpr int WTM = BM / WM, WTN = BN / WN;
     constexpr int TM = WTM / 16, TN = WTN / 16;
@@ -212,6 +225,7 @@ __device__ __forceinline__ void fused_epilogue(float4v (&acc)[BM / WM / 16][BN /
         const int g = m / rg;
         return (long long)g * E.row_stride + (m - g * rg);
     };
+    static_assert(!DR || BM <= NTH, "one row of the segment map per thread");
     wait_vmcnt<0>();
     __syncthreads();
     float *prm = reinterpret_cast<float *>(smem);
@@ -223,12 +237,16 @@ __device__ __forceinline__ void fused_epilogue(float4v (&acc)[BM / WM / 16][BN /
             prm[2 * BN + tid] = p.sh;
             prm[3 * BN + tid] = p.s2;
         }
+        if constexpr (DR) {
+            if (tid < BM) reinterpret_cast<int *>(prm + 4 * BN)[tid] = rsg;
+        }
     }
     __syncthreads();
     const EpiCols P{prm, prm + BN, prm + 2 * BN, prm + 3 * BN};
     using EM = EpiMap<WTN>;
     constexpr int LDT = EM::LDT;
-    float *st = prm + 4 * BN + wave * 32 * LDT;
+    const int *segl = reinterpret_cast<const int *>(prm + 4 * BN);  // DR: segment of tile row
+    float *st = prm + 4 * BN + (DR ? BM : 0) + wave * 32 * LDT;
     constexpr int CG = WTN / 8;
     constexpr int ITEMS = 32 * CG / 64;
     static_assert(ITEMS * 64 == 32 * CG, "items per lane");
@@ -243,6 +261,18 @@ __device__ __forceinline__ void fused_epilogue(float4v (&acc)[BM / WM / 16][BN /
     constexpr int NSL = (NCH <= 4 && ITEMS * NCH <= 6) ? NCH : 2;
     half8 rres[NSL][ITEMS], cold[2][ITEMS];
     unsigned mb[2][ITEMS];
+    Drop8 dr[DR ? ITEMS : 1];
+    auto load_drop = [&](auto ICc, auto K) {
+        constexpr int icp = decltype(ICc)::value, k = decltype(K)::value;
+        const int r = EM::row(k, lane), cg = EM::cg(k, lane);
+        const int ml = wm * WTM + icp * 32 + r, n = n0 + wn * WTN + 8 * cg;
+        dr[k].lo = dr[k].hi = float4v{1.f, 1.f, 1.f, 1.f};
+        if (m0 + ml < M && n < N) {
+            const float4v *q = reinterpret_cast<const float4v *>(E.drop + (long long)segl[ml] * E.ld_drop + n);
+            dr[k].lo = q[0];
+            dr[k].hi = q[1];
+        }
+    };
     auto prefetch_res = [&](auto ICc) {
         constexpr int icp = decltype(ICc)::value, sl = icp % NSL;
         static_for<ITEMS>([&](auto K) {
@@ -262,16 +292,23 @@ __device__ __forceinline__ void fused_epilogue(float4v (&acc)[BM / WM / 16][BN /
             const bool ok = m < M && n < N;
             cold[sl][k] = half8{};
             mb[sl][k] = 0xFFu;
-            if (ok && E.beta != 0.f) cold[sl][k] = load_h8((const h16 *)E.out + arow(m) * E.ldo + n);
+            if constexpr (!DR) {
+                if (ok && E.beta != 0.f) cold[sl][k] = load_h8((const h16 *)E.out + arow(m) * E.ldo + n);
+            }
             if (ok && E.mask_in) mb[sl][k] = E.mask_in[(arow(m) * E.ldo2 + n) >> 3];
         });
     };
     static_for<NSL - 1>([&](auto IC) { prefetch_res(IC); });
     prefetch(std::integral_constant<int, 0>{});
+    if constexpr (DR) static_for<ITEMS>([&](auto K) { load_drop(std::integral_constant<int, 0>{}, K); });
     static_for<NCH>([&](auto IC) {
         constexpr int ic = decltype(IC)::value, sl = ic & 1, slr = ic % NSL;
-        if constexpr (ic + NSL - 1 < NCH) prefetch_res(std::integral_constant<int, ic + NSL - 1>{});
-        if constexpr (ic + 1 < NCH) prefetch(std::integral_constant<int, ic + 1>{});
+        // (DR: after this chunk's accumulators have gone to LDS and freed their registers; still
+        // ahead of the chunk's first store)
+        if constexpr (!DR) {
+            if constexpr (ic + NSL - 1 < NCH) prefetch_res(std::integral_constant<int, ic + NSL - 1>{});
+            if constexpr (ic + 1 < NCH) prefetch(std::integral_constant<int, ic + 1>{});
+        }
         static_for<2>([&](auto I2) {
             static_for<TN>([&](auto J) {
                 const int c = J * 16 + (lane & 15);
@@ -281,6 +318,10 @@ __device__ __forceinline__ void fused_epilogue(float4v (&acc)[BM / WM / 16][BN /
                 });
             });
         });
+        if constexpr (DR) {
+            if constexpr (ic + NSL - 1 < NCH) prefetch_res(std::integral_constant<int, ic + NSL - 1>{});
+            if constexpr (ic + 1 < NCH) prefetch(std::integral_constant<int, ic + 1>{});
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -299,9 +340,11 @@ __device__ __forceinline__ void fused_epilogue(float4v (&acc)[BM / WM / 16][BN /
                     v[e] = x0[e];
                     v[e + 4] = x1[e];
                 }
-                epilogue8(E, P, arow(m), n, nl, v, cold[sl][k], rres[slr][k], mb[sl][k]);
+                if constexpr (DR) epilogue8<true>(E, P, arow(m), n, nl, v, cold[sl][k], rres[slr][k], mb[sl][k], &dr[k]);
+                else epilogue8(E, P, arow(m), n, nl, v, cold[sl][k], rres[slr][k], mb[sl][k]);
             }
-            if constexpr (CG % 4 == 0) {
+            if constexpr (DR && ic + 1 < NCH) load_drop(std::integral_constant<int, ic + 1>{}, K);
+            if constexpr (CG % 4 == 0 && !DR) {
                 // MXFP8 copy: the 4 lanes l..l+3 (l % 4 == 0) hold one 32-column block
                 if (E.out8) {
                     float amax = 0.f;
@@ -360,6 +403,9 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(int M, int N, int
     // operand modes; bit 3 (OP_MASKED) = the operand carries a bit mask (KfOperand.mask)
     constexpr int AMD = AM & 7, BMD = BMODE & 7;
     constexpr bool AMK = (AM & OP_MASKED) != 0, BMK = (BMODE & OP_MASKED) != 0, MK = AMK || BMK;
+    // bit 4 of the A mode (EPI_DROP): the epilogue applies KfEpilogue.drop to the rows A names
+    constexpr bool DR = (AM & EPI_DROP) != 0;
+    static_assert(!DR || (!WGRAD && !F8 && !MK), "drop: fp16 fused products without masked operands");
     static_assert(!MK || (ST == 2 && !F8), "masked operands: two-stage ring, fp16");
     using SCS = ScaleStager<F8 ? BM : 64, F8 ? BN : 64, NW, AMD>;  // used by MXFP8 only
     constexpr int SCB = F8 ? SCS::BYTES : 0;
@@ -376,7 +422,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(int M, int N, int
     constexpr int LPT = SA::NC + SB::NC + (F8 ? SCS::SPW : 0);  // LDS-DMA per thread per stage
     static_assert((SA::EVEN && SB::EVEN) || ST == 2, "uneven stagers need the vmcnt(0) ring");
     static_assert(ST >= 2 && ST <= 4, "stages");
-    static_assert(WGRAD || 4 * BN * 4 + (32 * EpiMap<WTN>::LDT * 4) * NW <= SmemSize<BM, BN, ST, SCB>::bytes,
+    static_assert(WGRAD || 4 * BN * 4 + (DR ? BM * 4 : 0) + (32 * EpiMap<WTN>::LDT * 4) * NW <=
+                               SmemSize<BM, BN, ST, SCB>::bytes,
                   "epilogue staging");
 
     __shared__ __attribute__((aligned(16))) char smem[SmemSize<BM, BN, ST, SCB>::bytes + (MK ? 4096 : 0)];
@@ -461,6 +508,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(int M, int N, int
     // address-taken and sends them to scratch)
     EpiPre epre{0.f, 0.f, 0.f, 1.f};
     if constexpr (!WGRAD) epre = epi_params<BN, 64 * NW>(E, N, n0, tid);
+    int rsg = 0;  // DR: the segment of tile row tid (KfEpilogue.row_seg), for the epilogue
+    if constexpr (DR) {
+        if (tid < BM && m0 + tid < M) rsg = E.row_seg[m0 + tid];
+    }
     // a two-part k-contiguous A ([x(t + d0) | x(t + d1)], K = 2 x part width): the K-steps
     // alternate between the parts, so each 64-column chunk of the source rows is fetched
     // for both parts while it is still in L2 (in part order the second pass misses)
@@ -563,7 +614,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_kernel(int M, int N, int
             G.bias_slab[(long long)split * N + n0 + tid] = bsum;
     } else {
         GEMM_TP(42);
-        fused_epilogue<BM, BN, WM, WN>(acc, smem, E, M, N, m0, n0, tid, lane, wave, &epre);
+        fused_epilogue<BM, BN, WM, WN, false, DR>(acc, smem, E, M, N, m0, n0, tid, lane, wave, &epre, rsg);
         if constexpr (F8) {
             if (G.eo && mt == n_mtiles - 1) {
                 // the clamped-edge row of the TDNN-F affine input gradient in fp16 (its second

@@ -19,7 +19,10 @@ int dz_index(const KfNet *net, const void *p) {
 // (the input of the layer being back-propagated). v = acc (+ bypass * g_cur):
 //   g_P = rne(v) when P itself has a bypass (its own input gradient needs it)
 //   dz_P = rne(v * bnscale_P * mask_P) for relu+BN layers, rne(v*bn2scale) for prefinal
-bool dx_epilogue(KfNet *net, int P, void *dz_out, void *g_out, KfEpilogue &E) {
+// A TDNN-F P whose forward applied a dropout mask: dz_P = rne(v * bnscale_P * drop_P * mask_P),
+// the table P's own (not that of the layer being back-propagated); g_P is not masked, the
+// bypass went round the dropout. compact_rows: the producing GEMM's rows are the compact row set.
+bool dx_epilogue(KfNet *net, int P, void *dz_out, void *g_out, KfEpilogue &E, bool compact_rows) {
     E = epi0();
     NetLayer &pl = net->layers[P];
     const Layer &L = pl.L;
@@ -32,6 +35,11 @@ bool dx_epilogue(KfNet *net, int P, void *dz_out, void *g_out, KfEpilogue &E) {
         case LayerType::TDNNF: {
             E.scale2 = pl.bn_scale;
             E.mask_in = pl.mask;
+            if (pl.drop_act) {
+                E.drop = pl.drop;
+                E.ld_drop = w;
+                E.row_seg = drop_rows(net, compact_rows);
+            }
             if (pl.bypass) {
                 E.out = g_out;
                 E.ldo = w;
@@ -416,7 +424,7 @@ int BackwardPass::step(int li, int ndone) {
            !two ? net->dbott : nbott % 3 == 0 ? net->dbott : nbott % 3 == 1 ? net->dbott2 : net->dbott3, KfEpilogue()};
     if (!side_wait(stepi - 3)) return -1;
     net->dz8_layer[flip] = -1;
-    if (s.want_dx && !dx_epilogue(net, nl.input, s.dz_next, s.g_next, s.E)) return -1;
+    if (s.want_dx && !dx_epilogue(net, nl.input, s.dz_next, s.g_next, s.E, nl.compact)) return -1;
     if (s.want_dx && s.to_full && !to_full_epilogue(s)) return -1;
     if (nl.bypass) {
         s.E.resid = gcur;
@@ -1048,6 +1056,10 @@ extern "C" int nnet_backward(KfNet *net, const void *out_grad) {
 extern "C" int nnet_backward_n(KfNet *net, const void *out_grad, int n) {
     if (net && net->ng_on) {
         set_err("backward_n: not supported with natural gradient on");
+        return -1;
+    }
+    if (net && drop_active(net)) {
+        set_err("backward_n: not supported with dropout on (nnet_set_dropout)");
         return -1;
     }
     return backward_impl(net, out_grad, n);

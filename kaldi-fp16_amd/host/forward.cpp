@@ -176,6 +176,11 @@ bool fwd_tdnnf(KfNet *net, int li, const void *x) {
         E2.ldr = din;
         E2.resid_alpha = (float)L.bypass_scale;
     }
+    if (nl.drop_act) {  // relu -> batchnorm -> dropout -> + bypass (the bypass is not masked)
+        E2.drop = nl.drop;
+        E2.ld_drop = dout;
+        E2.row_seg = drop_rows(net, nl.compact);
+    }
     return ck(kf_gemm_fused(T, dout, f8b ? nl.w8b.ld : kaff, &A2, &B2, &E2), "tdnnf affine");
 }
 
@@ -273,6 +278,71 @@ bool fwd_layer(KfNet *net, int li, const void *x, int T) {
     }
 }
 
+// weak, as network.cpp's: a host layer linked against a backend without the dropout kernels
+// never draws a mask
+#pragma weak kf_dropout_masks
+#pragma weak kf_row_seg
+
+// Per-sequence dropout of this forward: the masks of every layer with a
+// proportion > 0 in one launch, and the row -> sequence maps of the forward's row sets. The
+// step advances at every forward while the switch is on, masks drawn or not. Storage is made
+// at the first such forward and again only when a forward brings more sequences than any
+// before it: nothing is allocated per step.
+bool drop_prepare(KfNet *net) {
+    net->drop_live = false;
+    for (int li : net->drop_layers) net->layers[li].drop_act = false;
+    if (!drop_active(net)) return true;
+    if (net->fp8 || net->implicit_dz) {
+        set_err("forward: dropout is not supported in MXFP8 mode or with implicit dz");
+        return false;
+    }
+    const long long step = net->drop_step;
+    net->drop_step = (step + 1) & 0xFFFFFFFFll;
+    std::vector<KfDropLayer> tab;
+    for (int li : net->drop_layers)
+        if (net->layers[li].drop_p > 0.f) tab.push_back(KfDropLayer{nullptr, 0, 0, 0, 0.f, 0});
+    if (tab.empty()) return true;  // every proportion is 0: the identity
+    if (!kf_dropout_masks || !kf_row_seg) {
+        set_err("forward: this build of libkaldi_fp16 has no dropout kernels");
+        return false;
+    }
+    const int B = net->B > 0 ? net->B : 1, T = net->T;
+    if (B > net->drop_cap) {
+        const int cap = (B + 63) / 64 * 64;
+        for (int li : net->drop_layers) {
+            NetLayer &nl = net->layers[li];
+            if (!(nl.drop = (float *)net->dalloc((size_t)cap * nl.L.out_dim * 4))) {
+                set_err("forward: alloc dropout masks");
+                return false;
+            }
+        }
+        net->drop_cap = cap;
+    }
+    if (!net->row_seg) {
+        net->row_seg = (int32_t *)net->dalloc((size_t)net->max_T * 4);
+        net->row_seg_c = (int32_t *)net->dalloc((size_t)net->max_T * 4);
+        if (!net->row_seg || !net->row_seg_c) {
+            set_err("forward: alloc dropout row maps");
+            return false;
+        }
+    }
+    size_t k = 0;
+    for (int li : net->drop_layers) {
+        NetLayer &nl = net->layers[li];
+        if (!(nl.drop_p > 0.f)) continue;
+        tab[k++] = KfDropLayer{nl.drop, nl.L.out_dim, nl.L.out_dim, nl.drop_ord, nl.drop_p, 0};
+        nl.drop_act = true;
+    }
+    const int *so = net->B > 1 ? net->seq_off : nullptr;
+    if (!ck(kf_dropout_masks((int)tab.size(), tab.data(), B, net->drop_seed, step), "dropout masks") ||
+        !ck(kf_row_seg(net->row_seg, so, so ? B : 1, T, 0, 0), "dropout row map") ||
+        (net->rs.Tc > 0 && !ck(kf_row_seg(net->row_seg_c, so, so ? B : 1, T, net->rs.Tc0, net->rs.Tc), "dropout row map (compact rows)")))
+        return false;
+    net->drop_B = B;
+    net->drop_live = true;
+    return true;
+}
+
 int forward_impl(KfNet *net, const void *features, int T) {
     if (!on_device(net, "forward")) return -1;
     if (!refresh_wt(net)) return -1;
@@ -288,6 +358,7 @@ int forward_impl(KfNet *net, const void *features, int T) {
         const int tc0 = (T - 1) / 3 + 1;
         if (tc0 >= 4 * nt + 16 && tc0 + nt <= net->maxTc) net->rs = RowSet(T, tc0, nt);
     }
+    if (!drop_prepare(net)) return -1;
     for (size_t li = 0; li < net->layers.size(); ++li) {
         NetLayer &nl = net->layers[li];
         const void *x = act_of(net, nl.input);
@@ -309,6 +380,14 @@ extern "C" int nnet_forward(KfNet *net, const void *features, int T) {
         set_err("forward: the network has an ivector input; use nnet_forward_ivector");
         return -1;
     }
+    // the sequences nnet_set_sequences gave (their offsets are in seq_off), else one sequence
+    net->B = net->seq_row0.empty() ? 0 : (int)net->seq_row0.size() - 1;
+    if (net->B > 0 && net->seq_row0.back() != T && drop_active(net)) {
+        set_err("forward: T=" + std::to_string(T) + " is not the " + std::to_string(net->seq_row0.back()) +
+                " frames of the sequences given to nnet_set_sequences (dropout draws one mask per sequence)");
+        return -1;
+    }
+    if (net->B > 0 && net->seq_row0.back() != T) net->B = 0;
     return forward_impl(net, features, T);
 }
 // forward with per-sequence ivectors: ivectors fp16 [B x ivec_dim] on the device,

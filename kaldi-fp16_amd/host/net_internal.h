@@ -80,6 +80,13 @@ struct NetLayer {
     int wt_pi = -1, wt_K = 0, wt_N = 0;
     // conv input gradient, per-tap transposed weight blocks [fout x fin] (dgrad_wt)
     void *wtd = nullptr;
+    // per-sequence dropout (TDNN-F, kf_nnet.h nnet_set_dropout): the current proportion (< 0: no
+    // component), the layer's place in the generator's counter, its mask [drop_cap x out_dim]
+    // fp32, and whether the current forward drew and applied one
+    float drop_p = -1.f;
+    int drop_ord = -1;
+    float *drop = nullptr;
+    bool drop_act = false;
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -228,6 +235,18 @@ struct KfNet {
     long long ng_t = 0;      // steps so far: t < 10 or t % update_period == 0 updates the state
     bool ng_updating = false;  // this backward's steps
     bool ng_ran = false;     // ng_report holds a backward's report
+    // per-sequence dropout (kf_nnet.h nnet_set_dropout): the layers with a component,
+    // the switch, the generator's key and step, the sequence boundaries nnet_set_sequences gave
+    // (host copy; seq_off holds them on the device), the row -> sequence maps of the current
+    // forward (full rows / compact rows) and the sequences the mask tables hold
+    std::vector<int> drop_layers;
+    int drop_on = 0;
+    unsigned long long drop_seed = 0;
+    long long drop_step = 0;
+    std::vector<int> seq_row0;
+    int32_t *row_seg = nullptr, *row_seg_c = nullptr;
+    int drop_cap = 0, drop_B = 0;
+    bool drop_live = false;  // the current forward applied masks
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]
@@ -362,6 +381,15 @@ inline bool is_trainable(LayerType t) {
 inline int att_affine(const Layer &L) {
     const int ctx = 1 + L.num_left + L.num_right;
     return L.num_heads * (2 * L.key_dim + L.value_dim + ctx);
+}
+
+// dropout is switched on and the network has a layer it applies to (nnet_set_dropout)
+inline bool drop_active(const KfNet *net) { return net->drop_on && !net->drop_layers.empty(); }
+
+// the row -> sequence map (KfEpilogue.row_seg) of a GEMM whose rows are a compact layer's
+// (the compact row set when the forward has one) or the forward's frames
+inline const int32_t *drop_rows(const KfNet *net, bool compact) {
+    return compact && net->rs.Tc > 0 ? net->row_seg_c : net->row_seg;
 }
 
 // rows a layer's activations / gradients hold in the current forward

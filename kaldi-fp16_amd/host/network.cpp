@@ -307,6 +307,11 @@ static bool build_topology(KfNet *net, const char *xconfig_text, int max_frames,
                 nl.pb2 = add_param(net, n + ".AffineBias", 1, dout);
                 nl.bypass = L.bypass_scale > 0 && din == dout;
                 identity_bn(nl.hbn, dout);
+                if (L.dropout_proportion >= 0) {  // the layer has a dropout component
+                    nl.drop_p = (float)L.dropout_proportion;
+                    nl.drop_ord = (int)net->drop_layers.size();
+                    net->drop_layers.push_back((int)net->layers.size());
+                }
                 break;
             }
             case LayerType::Linear:
@@ -850,6 +855,10 @@ extern "C" int nnet_set_fp8(KfNet *net, int on) {
         set_err("set_fp8: not supported with natural gradient on (nnet_set_natural_gradient)");
         return -1;
     }
+    if (drop_active(net)) {
+        set_err("set_fp8: not supported with dropout on (nnet_set_dropout)");
+        return -1;
+    }
     net->fp8_dgrad = on != 2;
     if (!net->fp8) {
         const size_t T = (size_t)net->max_T;
@@ -885,6 +894,10 @@ extern "C" int nnet_set_fp8(KfNet *net, int on) {
 
 extern "C" int nnet_set_implicit_dz(KfNet *net, int on) {
     if (!net) return -1;
+    if (on && drop_active(net)) {
+        set_err("set_implicit_dz: not supported with dropout on (nnet_set_dropout)");
+        return -1;
+    }
     net->implicit_dz = on != 0;
     return 0;
 }
@@ -1629,3 +1642,137 @@ extern "C" int nnet_dp_debug_early(KfNet *net, int on) {
     return 0;
 }
 
+
+// ---------------------------------------------------------------------------
+// Per-sequence dropout of the TDNN-F layers (kf_nnet.h nnet_set_dropout): the
+// switches and tables. forward.cpp draws the masks and hands them to the affine GEMM's
+// epilogue, backward.cpp to the input-gradient GEMM that produces the layer's dz.
+// ---------------------------------------------------------------------------
+extern "C" int nnet_set_sequences(KfNet *net, const int *seq_row0, int B) {
+    if (!net) {
+        set_err("set_sequences: null network");
+        return -1;
+    }
+    if (!seq_row0 && B == 0) {  // back to one sequence
+        net->seq_row0.clear();
+        return 0;
+    }
+    if (!seq_row0 || B <= 0 || seq_row0[0] != 0 || seq_row0[B] <= 0 || seq_row0[B] > net->max_T || B > seq_row0[B]) {
+        set_err("set_sequences: needs B in [1, T], seq_row0[0] = 0 and T = seq_row0[B] in (0, max_frames]");
+        return -1;
+    }
+    for (int s = 0; s < B; ++s)
+        if (seq_row0[s + 1] <= seq_row0[s]) {
+            set_err("set_sequences: empty or unordered sequence " + std::to_string(s));
+            return -1;
+        }
+    if (net->master) {  // (a layout-only net keeps the host copy only)
+        if (!net->seq_off && !(net->seq_off = (int *)net->dalloc(((size_t)net->max_T + 1) * 4))) {
+            set_err("set_sequences: alloc seq offsets");
+            return -1;
+        }
+        if (bridge_transfer_int32(net->seq_off, seq_row0, (size_t)B + 1)) {
+            set_err("set_sequences: upload seq offsets");
+            return -1;
+        }
+    }
+    net->seq_row0.assign(seq_row0, seq_row0 + B + 1);
+    return 0;
+}
+
+extern "C" int nnet_dropout_layers(const KfNet *net, int *idx, int n) {
+    if (!net) return -1;
+    for (int i = 0; idx && i < n && i < (int)net->drop_layers.size(); ++i) idx[i] = net->drop_layers[i];
+    return (int)net->drop_layers.size();
+}
+
+extern "C" int nnet_set_dropout_proportion(KfNet *net, const char *layer, float p) {
+    if (!net) {
+        set_err("set_dropout_proportion: null network");
+        return -1;
+    }
+    if (!(p >= 0.f && p <= 0.5f)) {
+        set_err("set_dropout_proportion: the proportion must be in [0, 0.5], got " + std::to_string(p));
+        return -1;
+    }
+    if (!layer) {
+        for (int li : net->drop_layers) net->layers[li].drop_p = p;
+        return 0;
+    }
+    for (auto &nl : net->layers)
+        if (nl.L.name == layer) {
+            if (nl.drop_ord < 0) {
+                set_err(std::string("set_dropout_proportion: layer ") + layer + " has no dropout component");
+                return -1;
+            }
+            nl.drop_p = p;
+            return 0;
+        }
+    set_err(std::string("set_dropout_proportion: no layer ") + layer);
+    return -1;
+}
+
+extern "C" int nnet_dropout_proportion(const KfNet *net, const char *layer, float *p) {
+    if (net && layer)
+        for (const auto &nl : net->layers)
+            if (nl.L.name == layer) {
+                if (p) *p = nl.drop_ord < 0 ? -1.f : nl.drop_p;
+                return 0;
+            }
+    set_err(std::string("dropout_proportion: no layer ") + (layer ? layer : "(null)"));
+    return -1;
+}
+
+extern "C" int nnet_set_dropout(KfNet *net, int on, unsigned long long seed) {
+    if (!net) {
+        set_err("set_dropout: null network");
+        return -1;
+    }
+    if (on && !net->drop_layers.empty()) {
+        if (net->fp8 || net->implicit_dz) {
+            set_err("set_dropout: not supported in MXFP8 mode (nnet_set_fp8) or with implicit dz (nnet_set_implicit_dz)");
+            return -1;
+        }
+        if (net->drop_layers.size() > 65535) {
+            set_err("set_dropout: too many dropout layers");
+            return -1;
+        }
+    }
+    net->drop_on = on != 0;
+    net->drop_seed = seed;
+    return 0;
+}
+
+extern "C" int nnet_set_dropout_step(KfNet *net, long long step) {
+    if (!net || step < 0 || step > 0xFFFFFFFFll) {
+        set_err("set_dropout_step: the step must be in [0, 2^32)");
+        return -1;
+    }
+    net->drop_step = step;
+    return 0;
+}
+
+extern "C" long long nnet_dropout_step(const KfNet *net) { return net ? net->drop_step : -1; }
+
+extern "C" int nnet_dropout_mask(KfNet *net, const char *layer, float *host, int *B, int *dim) {
+    if (!on_device(net, "dropout_mask")) return -1;
+    for (auto &nl : net->layers) {
+        if (!layer || nl.L.name != layer) continue;
+        if (nl.drop_ord < 0 || !nl.drop_act || !nl.drop) {
+            set_err(std::string("dropout_mask: the last forward drew no mask for ") + layer +
+                    (nl.drop_ord < 0 ? " (no dropout component)" : " (dropout off or proportion 0)"));
+            return -1;
+        }
+        if (B) *B = net->drop_B;
+        if (dim) *dim = nl.L.out_dim;
+        // (ordered behind the forward on the current stream, and synchronises; fp32 read = 2x
+        // fp16 count, as nnet_update_stats)
+        if (host && bridge_read_fp16((uint16_t *)host, nl.drop, (size_t)net->drop_B * nl.L.out_dim * 2)) {
+            set_err("dropout_mask: read");
+            return -1;
+        }
+        return 0;
+    }
+    set_err(std::string("dropout_mask: no layer ") + (layer ? layer : "(null)"));
+    return -1;
+}

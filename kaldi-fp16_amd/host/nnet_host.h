@@ -53,6 +53,7 @@ struct Layer {  // layers.go:12-120 (specs flattened)
     // tdnnf
     int bottleneck = 0, time_stride = 3;
     double bypass_scale = 0.66;
+    double dropout_proportion = -1;  // -1: no dropout component (kf_nnet.h nnet_set_dropout)
     // prefinal
     int small_dim = 0, big_dim = 0;
     // output

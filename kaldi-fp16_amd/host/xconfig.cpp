@@ -268,6 +268,16 @@ bool ResolveLayers(const std::vector<LayerConfig> &cfgs, std::vector<Layer> &lay
                 L.bottleneck = bn;
                 L.time_stride = cfg.get_int("time-stride", 3);
                 L.bypass_scale = cfg.get_float("bypass-scale", 0.66);
+                // Kaldi: -1 (the default) = no dropout component; else the initial proportion of
+                // the layer's GeneralDropoutComponent (continuous: at most 0.5 keeps the mask >= 0)
+                auto it = cfg.params.find("dropout-proportion");
+                if (it != cfg.params.end()) {
+                    char *end = nullptr;
+                    const double v = strtod(it->second.c_str(), &end);
+                    if (it->second.empty() || !end || *end != 0 || !(v == -1.0 || (v >= 0.0 && v <= 0.5)))
+                        return fail("dropout-proportion must be -1 or in [0, 0.5], got \"" + it->second + "\"");
+                    L.dropout_proportion = v;
+                }
                 break;
             }
             case LayerType::Attention: {

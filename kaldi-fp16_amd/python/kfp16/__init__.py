@@ -169,6 +169,15 @@ _sig(nnet, "nnet_row_set", _i, _vp, C.POINTER(_i), C.POINTER(_i))
 _sig(nnet, "nnet_debug_backward", _i, _vp, _i, _ll)
 _sig(core, "kf_debug_spin", _i, _vp, _ll)
 _sig(nnet, "nnet_weights_changed", _i, _vp)
+# per-sequence dropout (kf_nnet.h nnet_set_dropout)
+_sig(nnet, "nnet_set_sequences", _i, _vp, _vp, _i)
+_sig(nnet, "nnet_dropout_layers", _i, _vp, C.POINTER(_i), _i)
+_sig(nnet, "nnet_set_dropout_proportion", _i, _vp, C.c_char_p, _f)
+_sig(nnet, "nnet_dropout_proportion", _i, _vp, C.c_char_p, C.POINTER(_f))
+_sig(nnet, "nnet_set_dropout", _i, _vp, _i, C.c_uint64)
+_sig(nnet, "nnet_set_dropout_step", _i, _vp, _ll)
+_sig(nnet, "nnet_dropout_step", _ll, _vp)
+_sig(nnet, "nnet_dropout_mask", _i, _vp, C.c_char_p, _vp, C.POINTER(_i), C.POINTER(_i))
 # kf_dp.h (RCCL data parallel)
 _sig(core, "kf_dp_last_error", C.c_char_p)
 _sig(core, "kf_dp_unique_id", _i, C.c_char_p)
@@ -621,6 +630,54 @@ class Network:
         mask (default off; kf_nnet.h nnet_set_implicit_dz)."""
         check(nnet.nnet_set_implicit_dz(self.h, int(on)), "nnet_set_implicit_dz")
 
+    # per-sequence dropout (kf_nnet.h nnet_set_dropout, DESIGN §21) -------
+    def set_sequences(self, seq_row0):
+        """The sequence boundaries (int[B+1] frame offsets 0 ... T) of later forward() calls with
+        that T; None: the whole input is one sequence."""
+        if seq_row0 is None:
+            check(nnet.nnet_set_sequences(self.h, None, 0), "nnet_set_sequences")
+            return
+        so = np.ascontiguousarray(seq_row0, dtype=np.int32)
+        check(nnet.nnet_set_sequences(self.h, so.ctypes.data, len(so) - 1), "nnet_set_sequences")
+
+    def dropout_layers(self) -> list:
+        """Names of the layers with a dropout component (dropout-proportion >= 0)."""
+        n = nnet.nnet_dropout_layers(self.h, None, 0)
+        idx = (_i * max(n, 1))()
+        nnet.nnet_dropout_layers(self.h, idx, n)
+        return [self.layers[idx[i]][0] for i in range(n)]
+
+    def set_dropout_proportion(self, p: float, layer: str = None):
+        """Kaldi's set-dropout-proportion: 0 <= p <= 0.5 on `layer`, or on every layer with a
+        component."""
+        check(nnet.nnet_set_dropout_proportion(self.h, layer.encode() if layer is not None else None, float(p)),
+              "nnet_set_dropout_proportion")
+
+    def dropout_proportion(self, layer: str) -> float:
+        """The layer's current proportion (-1: no component)."""
+        p = _f()
+        check(nnet.nnet_dropout_proportion(self.h, layer.encode(), C.byref(p)), "nnet_dropout_proportion")
+        return p.value
+
+    def set_dropout(self, on: bool, seed: int = 0):
+        """Train-mode dropout on / off (default off) and the mask generator's 64-bit seed."""
+        check(nnet.nnet_set_dropout(self.h, int(on), int(seed) & (2 ** 64 - 1)), "nnet_set_dropout")
+
+    def set_dropout_step(self, step: int):
+        """The step the next forward draws its masks with (replay)."""
+        check(nnet.nnet_set_dropout_step(self.h, int(step)), "nnet_set_dropout_step")
+
+    def dropout_step(self) -> int:
+        return int(nnet.nnet_dropout_step(self.h))
+
+    def dropout_mask(self, layer: str) -> np.ndarray:
+        """The mask [B x dim] float32 the last forward drew for `layer` (synchronises)."""
+        B, dim = _i(), _i()
+        check(nnet.nnet_dropout_mask(self.h, layer.encode(), None, C.byref(B), C.byref(dim)), "nnet_dropout_mask")
+        m = np.empty((B.value, dim.value), np.float32)
+        check(nnet.nnet_dropout_mask(self.h, layer.encode(), m.ctypes.data, None, None), "nnet_dropout_mask")
+        return m
+
     def dp_debug_early(self, on: bool):
         """Test hook: issue every gradient bucket before the backward runs (the
         negative control of the overlap tests)."""
@@ -676,7 +733,8 @@ class KfEpilogue(C.Structure):
                 ("resid_alpha", _f), ("out2", _vp), ("ldo2", _ll), ("scale2", _vp), ("mask_in", _vp),
                 ("out8", _vp), ("ldo8", _ll), ("scale8", _vp), ("out8_src", _i), ("edge_out", _vp),
                 ("edge_r0", _i), ("edge_r1", _i), ("edge_src", _i),
-                ("row_group", _i), ("row_stride", _i)]
+                ("row_group", _i), ("row_stride", _i),
+                ("drop", _vp), ("ld_drop", _ll), ("row_seg", _vp)]
 
 
 def operand(base, ld, rows, cols, kcontig, nparts=1, part_width=None, T=None, hout=1, hsrc=1,
@@ -792,6 +850,12 @@ _sig(core, "kf_ng_apply_scratch_bytes", _ll, _vp, _i, _vp, _i)
 _sig(core, "kf_ng_apply", _i, _vp, _ll, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp)
 _sig(core, "kf_ng_state_scratch_bytes", _ll, _vp, _i)
 _sig(core, "kf_ng_state", _i, _vp, _vp, _i, C.POINTER(KfNgOpts), _i, _vp, _vp, _vp, _vp, _vp, _vp)
+class KfDropLayer(C.Structure):
+    _fields_ = [("mask", _vp), ("ld", _ll), ("dim", _i), ("ordinal", _i), ("p", _f), ("reserved", _i)]
+
+
+_sig(core, "kf_dropout_masks", _i, _i, _vp, _i, C.c_uint64, _ll)
+_sig(core, "kf_row_seg", _i, _vp, _vp, _i, _i, _i, _i)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows_from", _i, _vp, _vp, _ll, _i, _i, _i, _i)

@@ -12,6 +12,9 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
                                      per-component max-change, L2 and learning-rate factors
   3a. (TrainConfig.natural_gradient) -> Network.set_natural_gradient: Kaldi's NG-SGD, the weight
                                      gradients preconditioned inside Network.backward
+  1a. (TrainConfig.dropout_schedule) -> Network.set_dropout_proportion before the forward: Kaldi's
+                                     --trainer.dropout-schedule on the TDNN-F layers' per-sequence
+                                     dropout, one mask row per eg
   5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
                                      ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
@@ -59,6 +62,58 @@ class TrainConfig:
     # the backward leaves the preconditioned weight gradients of the linear, output, tdnnf and
     # prefinal components for step 4, with either update. False: plain gradients, as before.
     natural_gradient: bool = False
+    # dropout_schedule: Kaldi's --trainer.dropout-schedule, e.g. '0,0@0.20,0.5@0.50,0': the
+    # proportion of every layer with a dropout component (xconfig dropout-proportion >= 0) as a
+    # piecewise-linear function of the fraction of data processed (dropout_proportion below), set
+    # before each forward; one mask row per eg, drawn from dropout_seed (under data parallel each
+    # rank folds its rank in, so ranks draw different masks). total_steps: the number of steps the
+    # fraction is derived from (steps taken / total_steps) when step() is not given one.
+    # '': nothing is called, as before.
+    dropout_schedule: str = ""
+    dropout_seed: int = 0
+    total_steps: int = 0
+
+
+def parse_dropout_schedule(schedule: str):
+    """[(fraction, proportion)] of Kaldi's 'v0,v1@f1,...,vN' form: the first value is at fraction
+    0, the last at 1, the ones between carry their fraction after '@', strictly increasing
+    inside (0, 1). Proportions must lie in [0, 0.5] (the continuous mask stays >= 0)."""
+    parts = [t.strip() for t in schedule.split(",")]
+    if len(parts) < 2 or any(not t for t in parts):
+        raise ValueError(f"dropout schedule {schedule!r}: needs at least a first and a last value")
+    pts = []
+    for i, tok in enumerate(parts):
+        ends = i == 0 or i == len(parts) - 1
+        if ends == ("@" in tok):
+            raise ValueError(f"dropout schedule {schedule!r}: {tok!r} "
+                             + ("is an end value and takes no fraction" if ends else "needs value@fraction"))
+        try:
+            if ends:
+                v, f = float(tok), 0.0 if i == 0 else 1.0
+            else:
+                a, b = tok.split("@")
+                v, f = float(a), float(b)
+        except ValueError:
+            raise ValueError(f"dropout schedule {schedule!r}: cannot read {tok!r}") from None
+        if not (0.0 <= v <= 0.5):
+            raise ValueError(f"dropout schedule {schedule!r}: proportion {v} outside [0, 0.5]")
+        if not ends and not (0.0 < f < 1.0):
+            raise ValueError(f"dropout schedule {schedule!r}: fraction {f} outside (0, 1)")
+        if pts and f <= pts[-1][0]:
+            raise ValueError(f"dropout schedule {schedule!r}: fractions must strictly increase")
+        pts.append((f, v))
+    return pts
+
+
+def dropout_proportion(schedule: str, fraction: float) -> float:
+    """The proportion Kaldi's dropout schedule gives at `fraction` of the data processed
+    (clamped to [0, 1]): piecewise linear between the schedule's points."""
+    pts = parse_dropout_schedule(schedule)
+    x = min(1.0, max(0.0, float(fraction)))
+    for (f0, v0), (f1, v1) in zip(pts, pts[1:]):
+        if x <= f1:
+            return v0 + (v1 - v0) * (x - f0) / (f1 - f0)
+    return pts[-1][1]
 
 
 def chain_rows(frame_offsets, num_frames, frames_per_seq, subsampling: int, left_context: int):
@@ -78,7 +133,7 @@ class EgsTrainer:
     """One network + objective, stepping on loader.TrainingBatch minibatches."""
 
     def __init__(self, xconfig: str, den_graph: dict, max_egs: int, max_frames: int,
-                 config: TrainConfig | None = None, grad_buffer_ptr: int | None = None):
+                 config: TrainConfig | None = None, grad_buffer_ptr: int | None = None, rank: int = 0):
         self.cfg = config or TrainConfig()
         self.net = Network(xconfig, max_frames=max_frames)
         self.P = self.net.layers[[n for n, *_ in self.net.layers].index("output")][3] \
@@ -99,11 +154,16 @@ class EgsTrainer:
         self.steps = 0  # steps taken
         if self.cfg.natural_gradient:
             self.net.set_natural_gradient(True)
+        if self.cfg.dropout_schedule:
+            parse_dropout_schedule(self.cfg.dropout_schedule)  # a malformed schedule fails here
+            # (each data-parallel rank its own masks: the rank folded into the seed)
+            self.net.set_dropout(True, (int(self.cfg.dropout_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
 
-    def step(self, batch, allreduce=None):
+    def step(self, batch, allreduce=None, fraction: float | None = None):
         """One TrainStep on `batch` (kfp16.egs.TrainingBatch). allreduce: optional callable
-        run between backward and SGD (data parallel). Asynchronous on the library stream;
-        call result() for the objective."""
+        run between backward and SGD (data parallel). fraction: the fraction of data processed,
+        for the dropout schedule (None: steps taken / TrainConfig.total_steps). Asynchronous on
+        the library stream; call result() for the objective."""
         T = batch.total_frames
         if T > self.max_frames or batch.feat_dim != 40:
             raise ValueError(f"batch of {T} frames x {batch.feat_dim} does not fit the trainer")
@@ -116,8 +176,16 @@ class EgsTrainer:
             batch.features_to_device(self.feat.ptr, 40)
         # rows the objective does not write must be zero for this batch
         core.bridge_gpu_memset(self.grad_out.ptr, 0, T * self.P * 2)
+        seq = np.append(np.asarray(batch.frame_offsets, np.int32), np.int32(T))
+        if self.cfg.dropout_schedule:
+            if fraction is None:
+                if self.cfg.total_steps <= 0:
+                    raise ValueError("a dropout schedule needs step(fraction=...) or TrainConfig.total_steps")
+                fraction = self.steps / self.cfg.total_steps
+            self.net.set_dropout_proportion(dropout_proportion(self.cfg.dropout_schedule, fraction))
+            if not self.ivec_dim:
+                self.net.set_sequences(seq)
         if self.ivec_dim:
-            seq = np.append(np.asarray(batch.frame_offsets, np.int32), np.int32(T))
             self.net.forward_ivector(self.feat.ptr, T, self.ivec.ptr, seq)
         else:
             self.net.forward(self.feat.ptr, T)
