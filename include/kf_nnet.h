@@ -233,6 +233,42 @@ long long nnet_dropout_step(const KfNet *net);
  * B and dim). An error when that forward drew none for it (dropout off, p = 0). */
 int nnet_dropout_mask(KfNet *net, const char *layer, float *host, int *B, int *dim);
 
+/* SpecAugment of the spec-augment-layer (kf_ops.h kf_specaug_rows): Kaldi's
+ * frequency mask (one zeroed band of at most Z = min(D, floor(D f + 0.5)) columns per sequence)
+ * and time mask (alternating kept and zeroed runs of frames, zeroed ones at most m frames long,
+ * about the share z of all frames) on the layer's input; zeroed elements are +0, nothing is
+ * rescaled. The layer reads the xconfig keys freq-max-proportion f in [0, 1] (default 0.5),
+ * time-zeroed-proportion z in [0, 1) (default 0.2) and time-mask-max-frames m >= 1 (default 10).
+ * Every call below but nnet_spec_augment_rows works on a layout-only net.
+ *
+ * nnet_spec_augment_layers: the spec-augment layers (nnet_layer_info indices) in the order of
+ * their ordinals: returns their number and writes the first n to idx (may be NULL). */
+int nnet_spec_augment_layers(const KfNet *net, int *idx, int n);
+/* a named spec-augment layer's options (each pointer may be NULL), and setting them, with the
+ * ranges of the xconfig keys */
+int nnet_spec_augment_opts(const KfNet *net, const char *layer, double *f, double *z, int *m);
+int nnet_set_spec_augment_opts(KfNet *net, const char *layer, double f, double z, int m);
+/* The switch (default off: test mode, the identity) and the generator's 64-bit seed. A layer is
+ * active in a forward when the switch is on and (Z > 0 or z > 0). An active layer has an
+ * activation of its own, fp16 [max_frames x dim] (allocated at the first forward that needs it,
+ * never per step), written by two launches (kf_specaug_rows, kf_specaug_apply) from the masks
+ * of (seed, step, the layer's ordinal); its consumers, nnet_activation and the backward (the
+ * weight gradient of the conv above) read that masked activation. An inactive layer stays an
+ * alias of its input: forward and backward are what they were, bit for bit. Sequences are those
+ * of nnet_set_sequences / nnet_forward_ivector; with the switch on, a forward whose T differs
+ * from the boundaries given fails. The feature's own step counter advances at every forward
+ * while the switch is on (on a net with such a layer) and wraps at 2^32. Switching on while a
+ * consumer of a spec-augment layer would read an MXFP8 copy of the layer's input
+ * (nnet_set_fp8) is an error, as is nnet_set_fp8 then. Backward through the layer into a
+ * trainable layer below it is not supported (Kaldi's recipes have none). */
+int nnet_set_spec_augment(KfNet *net, int on, unsigned long long seed);
+/* the step the next forward draws with (0 <= step < 2^32): replay */
+int nnet_set_spec_augment_step(KfNet *net, long long step);
+long long nnet_spec_augment_step(const KfNet *net);
+/* the row_band (kf_ops.h kf_specaug_rows) the last forward drew for a layer (synchronises):
+ * host int32 [T] (NULL: only T). An error when that forward drew none for it. */
+int nnet_spec_augment_rows(KfNet *net, const char *layer, int32_t *host, int *T);
+
 /* MXFP8 train step (BASELINE configs[4]): 1 = every TDNN-F / linear / prefinal / output
  * GEMM whose input has an MXFP8 copy runs on the fp8 MFMA (kf_ops.h MXFP8 operands);
  * the producing epilogues write those copies, weights are re-quantised on every

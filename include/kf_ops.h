@@ -435,6 +435,46 @@ int kf_dropout_masks(int n, const KfDropLayer *layers, int B, unsigned long long
  * step (the rule and its conditions as kf_gather_rows below). */
 int kf_row_seg(int32_t *row_seg, const int *dev_seq_off, int B, int T, int tc0, int tc);
 
+/* ---- SpecAugment masks of the spec-augment-layer (csrc/specaug.hip) ----
+ * Kaldi's GeneralDropoutComponent with specaugment-max-proportion followed by its
+ * SpecAugmentTimeMaskComponent. The rule:
+ *
+ * Layer keys: freq-max-proportion f in [0, 1] (default 0.5), time-zeroed-proportion z in
+ * [0, 1) (default 0.2), time-mask-max-frames m >= 1 (default 10). D = the layer's dim,
+ *   Z   = min(D, floor(D f + 0.5))                                     (max_bins)
+ *   m_n = max(1, floor(m (1 - z) / z)), on the host in double, capped at 2^31 - 1, unused
+ *         when z = 0                                                   (max_kept)
+ * Random numbers: the Philox4x32-10 of csrc/dropout.hip,
+ *   X(b, kind, i) = word i % 4 of Philox(counter {step, 0x80000000 | (2k + kind), b, i / 4},
+ *                                        key = the seed's low and high words)
+ * k the spec-augment layer's ordinal among spec-augment layers (the high bit keeps these
+ * streams apart from dropout's, whose ordinals are non-negative ints),
+ *   u24(x) = x >> 8,  randint(x, n) = (u24(x) n) >> 24, an integer in [0, n), exact in 64 bits.
+ * Frequency band of sequence b (kind 0): count = randint(X(b,0,0), Z + 1),
+ *   start = randint(X(b,0,1), D - count + 1); columns [start, start + count) are zeroed on
+ *   every frame of the sequence: one band per sequence.
+ * Time mask of sequence b (kind 1, only when z > 0): alternating regions tile the sequence's
+ *   frames from its first frame. Region 0 is zeroed iff (float)u24(X(b,1,0)) 2^-24 < (float)z;
+ *   region r is zeroed iff (region 0 is zeroed) XOR (r is odd);
+ *   len_r = 1 + randint(X(b,1,1 + r), zeroed_r ? m : m_n); the last region is clipped at the
+ *   sequence's end.
+ * Output element (r, c) is the input's bit pattern when the row is kept and c lies outside the
+ * band, else +0 (0x0000), also for a NaN, Inf or negative input: a select, not a multiply.
+ * No rescaling. Test mode is the identity.
+ *
+ * kf_specaug_rows: one launch writes the mask of every frame: row_band[r] = -1 when the whole
+ * row is zeroed, else start | count << 16, the band of the row's sequence (dim <= 32767).
+ * dev_seq_off device int[B + 1] (seq_off[0] = 0, seq_off[B] = T); B <= 1 or NULL: one sequence
+ * [0, T). One wavefront per sequence; no LDS, no atomics. 0 <= max_bins <= dim, 0 <= z < 1,
+ * max_zeroed >= 1, max_kept >= 1, ordinal < 2^30, 0 <= step < 2^32.
+ * kf_specaug_apply: the select on fp16 x [rows x dim] (leading dimension ldx) into y (ldy),
+ * x == y allowed. 16 bytes per lane when dim, ldx and ldy are multiples of 8 and both pointers
+ * are 16-byte aligned, else element by element; any dim in [1, 32767]. */
+int kf_specaug_rows(int32_t *row_band, const int *dev_seq_off, int B, int T, int dim, int max_bins, float z,
+                    int max_zeroed, int max_kept, unsigned ordinal, unsigned long long seed, long long step);
+int kf_specaug_apply(const void *x, long long ldx, void *y, long long ldy, long long rows, int dim,
+                     const int32_t *row_band);
+
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.
  * Every source row must exist: 3(tc0-1) <= T-1 and, with a tail (tc > tc0), its lowest row

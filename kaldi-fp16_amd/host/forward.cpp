@@ -1,6 +1,8 @@
 // forward.cpp — the forward pass of the C++ host layer (Network.Forward, forward.go:148-202,
 // and the per-layer forward functions): one function per layer kind, each a few fused
 // launches (network.cpp's header comment).
+#include <cmath>
+
 #include "net_internal.h"
 
 namespace {
@@ -260,7 +262,10 @@ bool fwd_layer(KfNet *net, int li, const void *x, int T) {
         case LayerType::Batchnorm:
             return ck(kf_bn_apply(x, nl.act, nl.per_seq ? net->B : T, L.out_dim, nl.bn_scale, nl.bn_shift), "batchnorm");
         case LayerType::SpecAugment:
-            return true;  // pass-through (forward.go:225-231, masking is a TODO there too)
+            // inactive: the alias of its input (forward.go:225-231 passes through). Active: the
+            // select by the row_band sa_prepare drew, into the layer's own activation
+            return !nl.sa_act ||
+                   ck(kf_specaug_apply(x, L.in_dim, nl.act, L.out_dim, T, L.out_dim, nl.sa_rows), "spec-augment apply");
         case LayerType::CombineFeatureMaps: return fwd_combine(net, nl, x, T);
         case LayerType::ConvReluBN: return fwd_conv(net, li, x, T);
         case LayerType::TDNNF: return fwd_tdnnf(net, li, x);
@@ -343,6 +348,53 @@ bool drop_prepare(KfNet *net) {
     return true;
 }
 
+#pragma weak kf_specaug_rows
+#pragma weak kf_specaug_apply
+
+// SpecAugment of this forward: which spec-augment layers mask (the switch on and
+// a band or a time mask to draw), their storage, and the row_band of each, one launch per
+// layer; fwd_layer applies it. The step advances at every forward while the switch is on, masks
+// drawn or not. The layer's activation and row_band are made at the first forward that needs
+// them: nothing is allocated per step.
+bool sa_prepare(KfNet *net) {
+    for (int li : net->sa_layers) net->layers[li].sa_act = false;
+    if (!sa_active(net)) return true;
+    const long long step = net->sa_step;
+    net->sa_step = (step + 1) & 0xFFFFFFFFll;
+    const int *so = net->B > 1 ? net->seq_off : nullptr;
+    for (int li : net->sa_layers) {
+        NetLayer &nl = net->layers[li];
+        const int dim = nl.L.out_dim, Z = sa_max_bins(nl);
+        if (Z <= 0 && !(nl.sa_z > 0)) continue;  // the identity: stays the alias
+        if (!kf_specaug_rows || !kf_specaug_apply) {
+            set_err("forward: this build of libkaldi_fp16 has no SpecAugment kernels");
+            return false;
+        }
+        // (an MXFP8 consumer through the alias is refused when the switches are set, network.cpp;
+        // nnet_set_row_subsampling admits no spec-augment layer into the compact row set)
+        if (!nl.act && !(nl.act = net->dalloc((size_t)net->max_T * dim * 2))) {
+            set_err("forward: alloc activation " + nl.L.name);
+            return false;
+        }
+        if (!nl.sa_rows && !(nl.sa_rows = (int32_t *)net->dalloc((size_t)net->max_T * 4))) {
+            set_err("forward: alloc SpecAugment rows " + nl.L.name);
+            return false;
+        }
+        // m_n = max(1, floor(m (1 - z) / z)) in double, capped at what an int holds
+        int max_kept = 1;
+        if (nl.sa_z > 0) {
+            const double mn = std::floor((double)nl.sa_m * (1.0 - nl.sa_z) / nl.sa_z);
+            max_kept = mn >= 2147483647.0 ? 2147483647 : mn < 1.0 ? 1 : (int)mn;
+        }
+        if (!ck(kf_specaug_rows(nl.sa_rows, so, so ? net->B : 1, net->T, dim, Z, (float)nl.sa_z, nl.sa_m, max_kept,
+                                (unsigned)nl.sa_ord, net->sa_seed, step),
+                "spec-augment rows"))
+            return false;
+        nl.sa_act = true;
+    }
+    return true;
+}
+
 int forward_impl(KfNet *net, const void *features, int T) {
     if (!on_device(net, "forward")) return -1;
     if (!refresh_wt(net)) return -1;
@@ -358,7 +410,7 @@ int forward_impl(KfNet *net, const void *features, int T) {
         const int tc0 = (T - 1) / 3 + 1;
         if (tc0 >= 4 * nt + 16 && tc0 + nt <= net->maxTc) net->rs = RowSet(T, tc0, nt);
     }
-    if (!drop_prepare(net)) return -1;
+    if (!drop_prepare(net) || !sa_prepare(net)) return -1;
     for (size_t li = 0; li < net->layers.size(); ++li) {
         NetLayer &nl = net->layers[li];
         const void *x = act_of(net, nl.input);
@@ -385,6 +437,11 @@ extern "C" int nnet_forward(KfNet *net, const void *features, int T) {
     if (net->B > 0 && net->seq_row0.back() != T && drop_active(net)) {
         set_err("forward: T=" + std::to_string(T) + " is not the " + std::to_string(net->seq_row0.back()) +
                 " frames of the sequences given to nnet_set_sequences (dropout draws one mask per sequence)");
+        return -1;
+    }
+    if (net->B > 0 && net->seq_row0.back() != T && sa_active(net)) {
+        set_err("forward: T=" + std::to_string(T) + " is not the " + std::to_string(net->seq_row0.back()) +
+                " frames of the sequences given to nnet_set_sequences (SpecAugment draws one mask per sequence)");
         return -1;
     }
     if (net->B > 0 && net->seq_row0.back() != T) net->B = 0;

@@ -48,7 +48,7 @@ struct NetLayer {
     std::vector<float> hbn[4], hbn2[4];                // host mean,var,gamma,beta
     float bn_eps = 1e-3f, bn_rms = 1.f, bn2_eps = 1e-3f, bn2_rms = 1.f;
     bool has_bn2 = false;
-    void *act = nullptr;      // fp16 [maxT x out_dim] (or alias of the input for spec-augment)
+    void *act = nullptr;      // fp16 [maxT x out_dim] (spec-augment: the alias of its input, see act_of)
     bool act_alias = false;
     uint8_t *mask = nullptr;  // relu bits
     void *aux = nullptr;      // tdnnf bottleneck / prefinal big
@@ -87,6 +87,14 @@ struct NetLayer {
     int drop_ord = -1;
     float *drop = nullptr;
     bool drop_act = false;
+    // spec-augment-layer (kf_nnet.h nnet_set_spec_augment): the layer's ordinal among such layers
+    // (-1: another kind), its options, the row_band [max_T] of its last active forward, and
+    // whether the current forward masked (act is then the layer's own buffer, not the alias)
+    int sa_ord = -1;
+    double sa_f = 0.5, sa_z = 0.2;
+    int sa_m = 10;
+    int32_t *sa_rows = nullptr;
+    bool sa_act = false;
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -247,6 +255,12 @@ struct KfNet {
     int32_t *row_seg = nullptr, *row_seg_c = nullptr;
     int drop_cap = 0, drop_B = 0;
     bool drop_live = false;  // the current forward applied masks
+    // SpecAugment (kf_nnet.h nnet_set_spec_augment): the spec-augment layers, the
+    // switch, the generator's key and the feature's own step
+    std::vector<int> sa_layers;
+    int sa_on = 0;
+    unsigned long long sa_seed = 0;
+    long long sa_step = 0;
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]
@@ -385,6 +399,12 @@ inline int att_affine(const Layer &L) {
 
 // dropout is switched on and the network has a layer it applies to (nnet_set_dropout)
 inline bool drop_active(const KfNet *net) { return net->drop_on && !net->drop_layers.empty(); }
+// SpecAugment is switched on and the network has a spec-augment layer (nnet_set_spec_augment)
+inline bool sa_active(const KfNet *net) { return net->sa_on && !net->sa_layers.empty(); }
+// Z = min(D, floor(D f + 0.5)): the widest band of a spec-augment layer
+inline int sa_max_bins(const NetLayer &nl) {
+    return std::min(nl.L.out_dim, (int)((double)nl.L.out_dim * nl.sa_f + 0.5));
+}
 
 // the row -> sequence map (KfEpilogue.row_seg) of a GEMM whose rows are a compact layer's
 // (the compact row set when the forward has one) or the forward's frames
@@ -408,7 +428,8 @@ inline const void *act_of(KfNet *net, int idx) {
     if (idx == -2) return net->ivec;
     if (idx < 0) return net->features;
     NetLayer &nl = net->layers[idx];
-    return nl.act_alias ? act_of(net, nl.input) : nl.act;
+    // (a spec-augment layer is an alias of its input unless this forward masked it)
+    return nl.act_alias && !nl.sa_act ? act_of(net, nl.input) : nl.act;
 }
 
 // ---- MXFP8 forward (network.cpp: set-up and weight quantisation) ----

@@ -347,6 +347,16 @@ static bool build_topology(KfNet *net, const char *xconfig_text, int max_frames,
                 break;
             }
             case LayerType::SpecAugment:
+                if (device && dout > 32767) {  // (kf_specaug_rows packs the band into 2 x 15 bits)
+                    set_err("spec-augment layer " + n + ": dim above 32767");
+                    return false;
+                }
+                nl.sa_f = L.freq_max_proportion;
+                nl.sa_z = L.time_zeroed_proportion;
+                nl.sa_m = L.time_mask_max_frames;
+                nl.sa_ord = (int)net->sa_layers.size();
+                net->sa_layers.push_back((int)net->layers.size());
+                break;
             case LayerType::CombineFeatureMaps:
                 break;
             default:
@@ -811,6 +821,22 @@ bool f8_producer(const KfNet *net, int idx) {
 }
 }  // namespace
 
+// A consumer of a spec-augment layer that, in MXFP8 mode, reads the MXFP8 copy of the layer's
+// input through the alias (net_internal.h in8): that copy is not masked. The consumer's name,
+// or "" when there is none.
+static std::string sa_mx_conflict(const KfNet *net) {
+    for (const auto &c : net->layers) {
+        if (c.input < 0 || net->layers[c.input].sa_ord < 0) continue;
+        if (c.L.type != LayerType::TDNNF && c.L.type != LayerType::Linear && c.L.type != LayerType::Prefinal &&
+            c.L.type != LayerType::Output)
+            continue;
+        int p = c.input;
+        while (p >= 0 && net->layers[p].L.type == LayerType::SpecAugment) p = net->layers[p].input;
+        if (p >= 0 && f8_producer(net, p)) return c.L.name;
+    }
+    return "";
+}
+
 static bool quantise_weights(KfNet *net, bool alloc) {
     std::vector<KfQuantJob> jobs;
     for (auto &nl : net->layers) {
@@ -857,6 +883,11 @@ extern "C" int nnet_set_fp8(KfNet *net, int on) {
     }
     if (drop_active(net)) {
         set_err("set_fp8: not supported with dropout on (nnet_set_dropout)");
+        return -1;
+    }
+    if (sa_active(net) && !sa_mx_conflict(net).empty()) {
+        set_err("set_fp8: with SpecAugment on (nnet_set_spec_augment) layer " + sa_mx_conflict(net) +
+                " would read the unmasked MXFP8 copy of a spec-augment layer's input");
         return -1;
     }
     net->fp8_dgrad = on != 2;
@@ -1775,4 +1806,94 @@ extern "C" int nnet_dropout_mask(KfNet *net, const char *layer, float *host, int
     }
     set_err(std::string("dropout_mask: no layer ") + (layer ? layer : "(null)"));
     return -1;
+}
+
+// ---------------------------------------------------------------------------
+// SpecAugment of the spec-augment layers (kf_nnet.h nnet_set_spec_augment): the
+// switch, the options and the step. forward.cpp draws and applies the masks.
+// ---------------------------------------------------------------------------
+static NetLayer *sa_layer(KfNet *net, const char *layer, const char *what) {
+    if (net && layer)
+        for (auto &nl : net->layers)
+            if (nl.L.name == layer) {
+                if (nl.sa_ord >= 0) return &nl;
+                set_err(std::string(what) + ": layer " + layer + " is not a spec-augment-layer");
+                return nullptr;
+            }
+    set_err(std::string(what) + ": no layer " + (layer ? layer : "(null)"));
+    return nullptr;
+}
+
+extern "C" int nnet_spec_augment_layers(const KfNet *net, int *idx, int n) {
+    if (!net) return -1;
+    for (int i = 0; idx && i < n && i < (int)net->sa_layers.size(); ++i) idx[i] = net->sa_layers[i];
+    return (int)net->sa_layers.size();
+}
+
+extern "C" int nnet_spec_augment_opts(const KfNet *net, const char *layer, double *f, double *z, int *m) {
+    const NetLayer *nl = sa_layer(const_cast<KfNet *>(net), layer, "spec_augment_opts");
+    if (!nl) return -1;
+    if (f) *f = nl->sa_f;
+    if (z) *z = nl->sa_z;
+    if (m) *m = nl->sa_m;
+    return 0;
+}
+
+extern "C" int nnet_set_spec_augment_opts(KfNet *net, const char *layer, double f, double z, int m) {
+    NetLayer *nl = sa_layer(net, layer, "set_spec_augment_opts");
+    if (!nl) return -1;
+    if (!(f >= 0.0 && f <= 1.0) || !(z >= 0.0 && z < 1.0) || m < 1) {
+        set_err("set_spec_augment_opts: needs freq-max-proportion in [0, 1], time-zeroed-proportion in [0, 1) and "
+                "time-mask-max-frames >= 1, got " + std::to_string(f) + ", " + std::to_string(z) + ", " + std::to_string(m));
+        return -1;
+    }
+    nl->sa_f = f;
+    nl->sa_z = z;
+    nl->sa_m = m;
+    return 0;
+}
+
+extern "C" int nnet_set_spec_augment(KfNet *net, int on, unsigned long long seed) {
+    if (!net) {
+        set_err("set_spec_augment: null network");
+        return -1;
+    }
+    if (on && net->fp8 && !net->sa_layers.empty() && !sa_mx_conflict(net).empty()) {
+        set_err("set_spec_augment: in MXFP8 mode (nnet_set_fp8) layer " + sa_mx_conflict(net) +
+                " would read the unmasked MXFP8 copy of a spec-augment layer's input");
+        return -1;
+    }
+    net->sa_on = on != 0;
+    net->sa_seed = seed;
+    return 0;
+}
+
+extern "C" int nnet_set_spec_augment_step(KfNet *net, long long step) {
+    if (!net || step < 0 || step > 0xFFFFFFFFll) {
+        set_err("set_spec_augment_step: the step must be in [0, 2^32)");
+        return -1;
+    }
+    net->sa_step = step;
+    return 0;
+}
+
+extern "C" long long nnet_spec_augment_step(const KfNet *net) { return net ? net->sa_step : -1; }
+
+extern "C" int nnet_spec_augment_rows(KfNet *net, const char *layer, int32_t *host, int *T) {
+    if (!on_device(net, "spec_augment_rows")) return -1;
+    NetLayer *nl = sa_layer(net, layer, "spec_augment_rows");
+    if (!nl) return -1;
+    if (!nl->sa_act || !nl->sa_rows) {
+        set_err(std::string("spec_augment_rows: the last forward drew no mask for ") + layer +
+                " (SpecAugment off, or no band and no time mask)");
+        return -1;
+    }
+    if (T) *T = net->T;
+    // (ordered behind the forward on the current stream, and synchronises; int32 read = 2x fp16
+    // count, as nnet_dropout_mask)
+    if (host && bridge_read_fp16((uint16_t *)host, nl->sa_rows, (size_t)net->T * 2)) {
+        set_err("spec_augment_rows: read");
+        return -1;
+    }
+    return 0;
 }

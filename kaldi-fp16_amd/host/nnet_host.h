@@ -54,6 +54,9 @@ struct Layer {  // layers.go:12-120 (specs flattened)
     int bottleneck = 0, time_stride = 3;
     double bypass_scale = 0.66;
     double dropout_proportion = -1;  // -1: no dropout component (kf_nnet.h nnet_set_dropout)
+    // spec-augment (kf_nnet.h nnet_set_spec_augment): Kaldi's xconfig defaults
+    double freq_max_proportion = 0.5, time_zeroed_proportion = 0.2;
+    int time_mask_max_frames = 10;
     // prefinal
     int small_dim = 0, big_dim = 0;
     // output

@@ -241,9 +241,33 @@ bool ResolveLayers(const std::vector<LayerConfig> &cfgs, std::vector<Layer> &lay
                 L.out_dim = L.in_dim;
                 L.target_rms = cfg.get_float("target-rms", 1.0);
                 break;
-            case LayerType::SpecAugment:
+            case LayerType::SpecAugment: {
                 L.out_dim = L.in_dim;
+                // Kaldi's xconfig defaults (nnet_host.h); a key that is present must be a number
+                // in its range (kf_nnet.h nnet_set_spec_augment)
+                auto num = [&](const char *key, double &v) {
+                    auto it = cfg.params.find(key);
+                    if (it == cfg.params.end()) return 0;
+                    char *end = nullptr;
+                    v = strtod(it->second.c_str(), &end);
+                    return it->second.empty() || !end || *end != 0 ? -1 : 1;
+                };
+                auto bad = [&](const char *key, const char *range) {
+                    return fail(std::string(key) + " must be " + range + ", got \"" + cfg.params.find(key)->second + "\"");
+                };
+                double v = 0;
+                int rc = num("freq-max-proportion", v);
+                if (rc < 0 || (rc > 0 && !(v >= 0.0 && v <= 1.0))) return bad("freq-max-proportion", "in [0, 1]");
+                if (rc > 0) L.freq_max_proportion = v;
+                rc = num("time-zeroed-proportion", v);
+                if (rc < 0 || (rc > 0 && !(v >= 0.0 && v < 1.0))) return bad("time-zeroed-proportion", "in [0, 1)");
+                if (rc > 0) L.time_zeroed_proportion = v;
+                rc = num("time-mask-max-frames", v);
+                if (rc < 0 || (rc > 0 && !(v >= 1.0 && v <= 2147483647.0 && v == (double)(long long)v)))
+                    return bad("time-mask-max-frames", "an integer >= 1");
+                if (rc > 0) L.time_mask_max_frames = (int)v;
                 break;
+            }
             case LayerType::CombineFeatureMaps:
                 L.height = cfg.get_int("height", 0);
                 L.nf1 = cfg.get_int("num-filters1", 1);

@@ -118,6 +118,7 @@ _sig(core, "ops_gemm", _i, _vp, _i, _i, _i, _f, _vp, _i, _vp, _i, _f, _vp, _i)
 _sig(core, "ops_cublas_create", _vp)
 _sig(core, "ops_cublas_destroy", None, _vp)
 _sig(core, "ops_log_softmax", _i, _vp, _i, _i)
+_sig(core, "ops_copy", _i, _vp, _vp, _i)  # (here, not only in refpath: undeclared, ctypes passes pointers as 32-bit ints)
 
 # ---------------------------------------------------------------- nnet_*
 _sig(nnet, "nnet_create", _vp, C.c_char_p, _i)
@@ -178,6 +179,14 @@ _sig(nnet, "nnet_set_dropout", _i, _vp, _i, C.c_uint64)
 _sig(nnet, "nnet_set_dropout_step", _i, _vp, _ll)
 _sig(nnet, "nnet_dropout_step", _ll, _vp)
 _sig(nnet, "nnet_dropout_mask", _i, _vp, C.c_char_p, _vp, C.POINTER(_i), C.POINTER(_i))
+# SpecAugment (kf_nnet.h nnet_set_spec_augment)
+_sig(nnet, "nnet_spec_augment_layers", _i, _vp, C.POINTER(_i), _i)
+_sig(nnet, "nnet_spec_augment_opts", _i, _vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i))
+_sig(nnet, "nnet_set_spec_augment_opts", _i, _vp, C.c_char_p, C.c_double, C.c_double, _i)
+_sig(nnet, "nnet_set_spec_augment", _i, _vp, _i, C.c_uint64)
+_sig(nnet, "nnet_set_spec_augment_step", _i, _vp, _ll)
+_sig(nnet, "nnet_spec_augment_step", _ll, _vp)
+_sig(nnet, "nnet_spec_augment_rows", _i, _vp, C.c_char_p, _vp, C.POINTER(_i))
 # kf_dp.h (RCCL data parallel)
 _sig(core, "kf_dp_last_error", C.c_char_p)
 _sig(core, "kf_dp_unique_id", _i, C.c_char_p)
@@ -678,6 +687,46 @@ class Network:
         check(nnet.nnet_dropout_mask(self.h, layer.encode(), m.ctypes.data, None, None), "nnet_dropout_mask")
         return m
 
+    # SpecAugment (kf_nnet.h nnet_set_spec_augment) -----------
+    def spec_augment_layers(self) -> list:
+        """Names of the spec-augment layers, in the order of their ordinals."""
+        n = nnet.nnet_spec_augment_layers(self.h, None, 0)
+        idx = (_i * max(n, 1))()
+        nnet.nnet_spec_augment_layers(self.h, idx, n)
+        return [self.layers[idx[i]][0] for i in range(n)]
+
+    def spec_augment_opts(self, layer: str):
+        """(freq-max-proportion, time-zeroed-proportion, time-mask-max-frames) of `layer`."""
+        f, z, m = C.c_double(), C.c_double(), _i()
+        check(nnet.nnet_spec_augment_opts(self.h, layer.encode(), C.byref(f), C.byref(z), C.byref(m)),
+              "nnet_spec_augment_opts")
+        return f.value, z.value, m.value
+
+    def set_spec_augment_opts(self, layer: str, f: float, z: float, m: int):
+        """f in [0, 1], z in [0, 1), m >= 1: the xconfig keys' ranges."""
+        check(nnet.nnet_set_spec_augment_opts(self.h, layer.encode(), float(f), float(z), int(m)),
+              "nnet_set_spec_augment_opts")
+
+    def set_spec_augment(self, on: bool, seed: int = 0):
+        """Train-mode SpecAugment on / off (default off) and the mask generator's 64-bit seed."""
+        check(nnet.nnet_set_spec_augment(self.h, int(on), int(seed) & (2 ** 64 - 1)), "nnet_set_spec_augment")
+
+    def set_spec_augment_step(self, step: int):
+        """The step the next forward draws its masks with (replay)."""
+        check(nnet.nnet_set_spec_augment_step(self.h, int(step)), "nnet_set_spec_augment_step")
+
+    def spec_augment_step(self) -> int:
+        return int(nnet.nnet_spec_augment_step(self.h))
+
+    def spec_augment_rows(self, layer: str) -> np.ndarray:
+        """int32 [T]: per frame of the last forward -1 (zeroed) or the band start | count << 16
+        of its sequence (synchronises)."""
+        T = _i()
+        check(nnet.nnet_spec_augment_rows(self.h, layer.encode(), None, C.byref(T)), "nnet_spec_augment_rows")
+        rows = np.empty(T.value, np.int32)
+        check(nnet.nnet_spec_augment_rows(self.h, layer.encode(), rows.ctypes.data, None), "nnet_spec_augment_rows")
+        return rows
+
     def dp_debug_early(self, on: bool):
         """Test hook: issue every gradient bucket before the backward runs (the
         negative control of the overlap tests)."""
@@ -856,6 +905,8 @@ class KfDropLayer(C.Structure):
 
 _sig(core, "kf_dropout_masks", _i, _i, _vp, _i, C.c_uint64, _ll)
 _sig(core, "kf_row_seg", _i, _vp, _vp, _i, _i, _i, _i)
+_sig(core, "kf_specaug_rows", _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint64, _ll)
+_sig(core, "kf_specaug_apply", _i, _vp, _ll, _vp, _ll, _ll, _i, _vp)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows", _i, _vp, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_scatter_rows_from", _i, _vp, _vp, _ll, _i, _i, _i, _i)

@@ -15,6 +15,8 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
   1a. (TrainConfig.dropout_schedule) -> Network.set_dropout_proportion before the forward: Kaldi's
                                      --trainer.dropout-schedule on the TDNN-F layers' per-sequence
                                      dropout, one mask row per eg
+  1b. (TrainConfig.spec_augment)     -> Network.set_spec_augment: Kaldi's SpecAugment on the
+                                     spec-augment-layers, one band and one time mask per eg
   5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
                                      ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
@@ -72,6 +74,11 @@ class TrainConfig:
     dropout_schedule: str = ""
     dropout_seed: int = 0
     total_steps: int = 0
+    # spec_augment: Network.set_spec_augment on the xconfig's spec-augment-layers (Kaldi's
+    # frequency and time masks), one sequence per eg, drawn from spec_augment_seed
+    # (under data parallel each rank folds its rank in, as for dropout). False: nothing is called.
+    spec_augment: bool = False
+    spec_augment_seed: int = 0
 
 
 def parse_dropout_schedule(schedule: str):
@@ -158,6 +165,8 @@ class EgsTrainer:
             parse_dropout_schedule(self.cfg.dropout_schedule)  # a malformed schedule fails here
             # (each data-parallel rank its own masks: the rank folded into the seed)
             self.net.set_dropout(True, (int(self.cfg.dropout_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
+        if self.cfg.spec_augment:
+            self.net.set_spec_augment(True, (int(self.cfg.spec_augment_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
 
     def step(self, batch, allreduce=None, fraction: float | None = None):
         """One TrainStep on `batch` (kfp16.egs.TrainingBatch). allreduce: optional callable
@@ -183,8 +192,8 @@ class EgsTrainer:
                     raise ValueError("a dropout schedule needs step(fraction=...) or TrainConfig.total_steps")
                 fraction = self.steps / self.cfg.total_steps
             self.net.set_dropout_proportion(dropout_proportion(self.cfg.dropout_schedule, fraction))
-            if not self.ivec_dim:
-                self.net.set_sequences(seq)
+        if (self.cfg.dropout_schedule or self.cfg.spec_augment) and not self.ivec_dim:
+            self.net.set_sequences(seq)
         if self.ivec_dim:
             self.net.forward_ivector(self.feat.ptr, T, self.ivec.ptr, seq)
         else:

@@ -58,5 +58,5 @@ if __name__ == "__main__":
         r = new[k]
         alloc, waves, wgs = occupancy(r)
         print("%-14s %-62s vgpr %3d agpr %2d sgpr %3d scratch %d lds %6d | alloc %3d, %d waves/SIMD, %d workgroups/CU" % (
-            r["unit"], re.sub(r"^void ", "", demangle(k)).split("(")[0][:62], r["vgpr"], r["agpr"], r["sgpr"], r["scratch"],
+            r["unit"], re.sub(r"^void ", "", demangle(k)).replace("(anonymous namespace)::", "").split("(")[0][:62], r["vgpr"], r["agpr"], r["sgpr"], r["scratch"],
             r["lds"], alloc, waves, wgs))
