@@ -99,7 +99,11 @@ void kf_chain_free(KfChain *c);
 /* One objective + derivative for the minibatch, asynchronous on kf_get_stream().
  * nnet_output / out_grad: fp16 device matrices of num_rows rows, leading dims ld / ldg
  * (>= P). seq_row0 / seq_frames: host arrays [nseq]; every supervised row must lie
- * inside the matrix. */
+ * inside the matrix. A sequence of 0 frames writes no row and has all-zero statistics:
+ * it counts in num_seqs only. The per-sequence layout is uploaded again only when it
+ * changes: another batch (each kf_num_batch_create / _refill gives the batch a new
+ * identity, so a batch created where a freed one lay is another batch), other rows,
+ * frames, stride or nnet_output. */
 int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
                      const void *nnet_output, long long ld, long long num_rows, int nseq,
                      const int32_t *seq_row0, const int32_t *seq_frames, int stride,

@@ -29,6 +29,7 @@
 #include "../../include/kf_chain.h"
 #include "../../include/kf_ops.h"
 
+#include <atomic>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -555,8 +556,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t den_rsrc(const void *base) {
 }
 // Exchange word access. LOC: every block of the sequence runs on one XCD, so they share
 // one L2 — plain stores (written through the CU's L1 into that L2, acknowledged there)
-// and sc0 loads (which miss the L1) hand the data over without the write-through to
-// memory that agent scope (sc1) needs across XCDs. `base` is uniform, `i` a word index.
+// and sc1 loads (which bypass the reading CU's L1 and are served by that L2) hand the data
+// over without the write-through to memory that agent-scope stores need across XCDs.
+// (An sc0 load hits the L1 like a plain one: the partial-sum slots, rewritten every other
+// frame, then came back stale whenever the state rows were too small to evict them.)
+// `base` is uniform, `i` a word index.
 template <bool LOC>
 __device__ __forceinline__ void x_st(float *base, int i, float v) {
     if constexpr (LOC)
@@ -567,7 +571,7 @@ __device__ __forceinline__ void x_st(float *base, int i, float v) {
 template <bool LOC>
 __device__ __forceinline__ float x_ld(const float *base, int i) {
     if constexpr (LOC)
-        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(den_rsrc(base), i * 4, 0, 1 /* sc0 */));
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(den_rsrc(base), i * 4, 0, 16 /* sc1 */));
     else
         return ld_sc1(base + i);
 }
@@ -1225,6 +1229,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_post(const DenDev g, const 
 
     const int T = r.frames[seq];
     const int t0 = fb * POST_FRAMES, t1 = min(T, t0 + POST_FRAMES);
+    // a sequence without frames adds nothing to kf_chain_result (its statistics would
+    // otherwise be those of the sequence an earlier compute ran in this slot)
+    if (MODE == DEN_PRODUCT && T <= 0 && fb == 0 && tid < 8) r.stats[(size_t)seq * 8 + tid] = 0.0f;
     if (t0 >= t1) return;
     const long long row0 = r.row0[seq];
     const XT *nnet = reinterpret_cast<const XT *>(r.nnet);
@@ -2589,10 +2596,17 @@ struct KfDenGraph {
     }
 };
 
+// Process-unique identity of a numerator batch's contents: kf_chain_compute's layout cache
+// is keyed on it and not on the batch's address, which the allocator hands out again
+// after a free (a new batch of the same shape would inherit the freed batch's
+// descriptors). 0 is never drawn: it is the cache's "nothing cached".
+static std::atomic<unsigned long long> g_num_batch_gen{0};
+static unsigned long long next_num_batch_gen() { return ++g_num_batch_gen; }
+
 struct KfNumBatch {
     NumDevice *nd = nullptr;
     std::vector<int> S;
-    unsigned gen = 0;                  // bumped by every refill (kf_chain_compute's layout cache)
+    unsigned long long gen = next_num_batch_gen();  // redrawn by every refill
     // kf_num_batch_refill: device blob and its pinned host staging (grow only)
     int32_t *d_blob = nullptr;
     size_t d_cap = 0;                  // int32 entries
@@ -2626,8 +2640,7 @@ struct KfChain {
     int *d_frames = nullptr;
     float *d_num_total = nullptr;
     // cache of the last run's layout (re-uploaded only when it changes)
-    const KfNumBatch *last_num = nullptr;
-    unsigned last_gen = 0;
+    unsigned long long last_gen = 0;   // KfNumBatch::gen of the cached layout, 0 = none
     // pinned staging of the layout upload: two slots, each reused after its copy's event
     char *h_stage[2] = {nullptr, nullptr};
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
@@ -2835,7 +2848,7 @@ extern "C" int kf_num_batch_refill(KfNumBatch *b, int nseq, const int32_t *state
     num_descs(hs, offs, b->d_blob, b->nd);
     b->S.clear();
     for (auto &h : hs) b->S.push_back(h.S);
-    ++b->gen;
+    b->gen = next_num_batch_gen();
     return 0;
 }
 extern "C" void kf_num_batch_free(KfNumBatch *b) {
@@ -2910,7 +2923,7 @@ extern "C" int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChain
     hipStream_t st = kf_stream();
     // a refilled numerator batch (kf_num_batch_refill): its copy lands before anything reads it
     if (num->ev_copy) hipStreamWaitEvent(st, num->ev_copy, 0);
-    bool same = c->last_num == num && c->last_gen == num->gen && c->last_nseq == nseq && c->last_stride == stride &&
+    bool same = c->last_gen == num->gen && c->last_nseq == nseq && c->last_stride == stride &&
                 c->last_nnet == nnet_output && c->last_ld == ld && c->last_rows == num_rows &&
                 std::equal(seq_row0, seq_row0 + nseq, c->last_row0.begin(), c->last_row0.end()) &&
                 std::equal(seq_frames, seq_frames + nseq, c->last_frames.begin(),
@@ -2994,11 +3007,10 @@ extern "C" int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChain
                                  hipMemcpyHostToDevice, st) == hipSuccess;
         cp = cp && hipEventRecord(c->ev_stage[slot], st) == hipSuccess;
         if (!cp) {
-            c->last_num = nullptr;
+            c->last_gen = 0;
             kfc_set_error("kf_chain_compute: layout upload failed");
             return -1;
         }
-        c->last_num = num;
         c->last_gen = num->gen;
         c->last_nseq = nseq;
         c->last_stride = stride;
