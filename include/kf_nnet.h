@@ -269,6 +269,33 @@ long long nnet_spec_augment_step(const KfNet *net);
  * host int32 [T] (NULL: only T). An error when that forward drew none for it. */
 int nnet_spec_augment_rows(KfNet *net, const char *layer, int32_t *host, int *T);
 
+/* Training-mode BatchNorm (default off): Kaldi's BatchNormComponent in training
+ * mode for the BatchNorms the switch governs, today BatchNorm 0 of every tdnnf-layer
+ * (nnet_bn_train_layers: their layer indices; returns their number). While it is on, each
+ * nnet_forward normalises such a layer by the statistics of its own rows (all rows the layer
+ * computes, every frame once; kf_ops.h kf_bn_train_stats), nnet_backward differentiates through
+ * them, and the layer accumulates count, sum and sumsq in double. The frozen statistics
+ * (nnet_set_bn) are untouched and apply again when the switch is off. The other BatchNorms
+ * (conv-relu-batchnorm, prefinal, attention, batchnorm-component) stay frozen.
+ *   nnet_bn_batch_stats: mean / var [out_dim] of the last forward (fp32; either may be NULL).
+ *   nnet_bn_stats: the accumulators (count; sum, sumsq [out_dim]; any may be NULL).
+ *   nnet_bn_zero_stats: clears them (Kaldi's ZeroComponentStats at the start of a job).
+ *   nnet_bn_commit: every governed layer with count > 0 takes mean = sum / count,
+ *     var = sumsq / count - mean^2 (floored at 0) as its frozen statistics through nnet_set_bn
+ *     (gamma 1, beta 0, the layer's eps and target_rms); returns the layers committed, -1 on error.
+ * `which` is the BatchNorm index of nnet_set_bn (1: prefinal-layer's second one; only 0 of a
+ * tdnnf-layer is governed today). Composes with dropout, SpecAugment, natural gradient,
+ * nnet_update and the orthonormal constraint. Refused, in either order of the two calls: MXFP8
+ * mode (nnet_set_fp8), implicit dz, row subsampling (the compact row set's scratch row and
+ * inexact tail rows are not rows of the layer), a bound data-parallel communicator (the
+ * statistics would be each rank's own), and nnet_backward_n. */
+int nnet_set_bn_train(KfNet *net, int on);
+int nnet_bn_train_layers(const KfNet *net, int *idx, int n);
+int nnet_bn_batch_stats(KfNet *net, const char *layer, int which, float *mean, float *var);
+int nnet_bn_stats(KfNet *net, const char *layer, int which, double *count, double *sum, double *sumsq);
+int nnet_bn_zero_stats(KfNet *net);
+int nnet_bn_commit(KfNet *net);
+
 /* MXFP8 train step (BASELINE configs[4]): 1 = every TDNN-F / linear / prefinal / output
  * GEMM whose input has an MXFP8 copy runs on the fp8 MFMA (kf_ops.h MXFP8 operands);
  * the producing epilogues write those copies, weights are re-quantised on every

@@ -475,6 +475,42 @@ int kf_specaug_rows(int32_t *row_band, const int *dev_seq_off, int B, int T, int
 int kf_specaug_apply(const void *x, long long ldx, void *y, long long ldy, long long rows, int dim,
                      const int32_t *row_band);
 
+/* ---- Training-mode BatchNorm of the TDNN-F layers (csrc/batchnorm.hip) ----
+ * Kaldi's BatchNormComponent in training mode on r = rne_fp16(relu(affine + bias)), an fp16
+ * [rows x D] tensor the affine GEMM wrote (no scale, shift, dropout or bypass in its epilogue).
+ * Every fp16 tensor: 16-byte aligned, ld >= D, ld % 8 == 0; D % 8 == 0; the per-column fp32
+ * arrays of the apply entries 16-byte aligned. Column sums are taken in double, in a fixed order,
+ * without atomics (two launches: per chunk of 256 rows, then over the chunks), so every entry
+ * replays bit for bit. The partials live in the current stream's scratch.
+ *
+ * kf_bn_train_stats, per column c over the n = rows rows:
+ *   mean = sum r / n,  var = max(0, sum r^2 / n - mean^2),
+ *   scale = target_rms (var + eps)^-1/2,  shift = -mean scale
+ * in double, stored in fp32. With the accumulators (device doubles: count [1], sum [D],
+ * sumsq [D]; all three or none): count += n, sum += sum r, sumsq += sum r^2.
+ * kf_bn_train_apply: out = rne_fp16(((r scale + shift) drop[row_seg[row]]) + alpha resid), the
+ *   fp32 operations of the fused epilogue in its order (fmaf, multiply, fmaf); drop (fp32
+ *   [B x ld_drop], ld_drop % 4 == 0, with row_seg) and resid (fp16, ldr) are optional.
+ * kf_bn_train_bwd_stats: with g the gradient at the layer's output, dy = g drop[row_seg[row]] and
+ *   yhat = (r scale + shift) / target_rms:  a = sum dy / n,  b = sum dy yhat / n  (fp32 stores of
+ *   double sums; sum dy yhat = (scale sum dy r + shift sum dy) / target_rms).
+ * kf_bn_train_bwd_apply: dz = rne_fp16(scale (dy - a - yhat b) relu_bit), the exact derivative
+ *   through the batch statistics (eps included: scale carries it), Kaldi's
+ *   BatchNormComponent::Backprop; evaluated in double. relu_bit is bit (row ld_mask + c) of the
+ *   forward's ReLU mask (ld_mask in bits, a multiple of 8). dz may not alias g or r. */
+int kf_bn_train_stats(const void *r, long long ld, int rows, int D, float eps, float target_rms, float *mean,
+                      float *var, float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq);
+int kf_bn_train_apply(const void *r, long long ld, int rows, int D, const float *scale, const float *shift,
+                      const float *drop, long long ld_drop, const int32_t *row_seg, const void *resid, long long ldr,
+                      float alpha, void *out, long long ldo);
+int kf_bn_train_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                          const float *scale, const float *shift, float target_rms, const float *drop,
+                          long long ld_drop, const int32_t *row_seg, float *a, float *b);
+int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                          const float *scale, const float *shift, float target_rms, const float *a, const float *b,
+                          const float *drop, long long ld_drop, const int32_t *row_seg, const uint8_t *mask,
+                          long long ld_mask, void *dz, long long lddz);
+
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.
  * Every source row must exist: 3(tc0-1) <= T-1 and, with a tail (tc > tc0), its lowest row

@@ -1,0 +1,381 @@
+// batchnorm.hip — training-mode BatchNorm of the TDNN-F layers (kf_ops.h kf_bn_train_*,
+// DESIGN.md §23): Kaldi's BatchNormComponent in training mode. The affine GEMM writes
+// r = rne_fp16(relu(affine + bias)) and its ReLU mask; the four entries here normalise r by the
+// minibatch's own column statistics and differentiate through them.
+//
+// Column sums are taken in double, in a fixed order and without atomics, so a step replays bit
+// for bit: a first launch reduces each chunk of kChunk rows to one partial per column (a lane
+// walks its rows in order, the 4 row lanes of a workgroup are summed in order through LDS), a
+// second sums the chunks in a fixed order (eight interleaved runs per column, added in order
+// through LDS) and finishes. All four entries are bound by HBM: every input is read once with
+// 16-byte lanes along the row, every output written once.
+#include "kf_common.h"
+#include "../../include/kf_ops.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kColLanes = 64;               // lanes along a row, 8 halves (16 bytes) each: a wave reads 1 KB
+constexpr int kRowLanes = kThreads / kColLanes;
+constexpr int kSlab = kColLanes * 8;        // columns of a workgroup
+// rows of a chunk: 96,000 x 1536 (the benchmark model's TDNN-F output) gives 375 x 3 = 1125
+// workgroups of 256 threads, more than four per CU of the MI355X's 256
+constexpr int kChunk = 256;
+// the second launch: a workgroup finishes kFinCols columns, kFinLanes lanes per column; lane l sums
+// the chunks l, l + kFinLanes, ... in order, then the lanes are added in order
+constexpr int kFinCols = 32;
+constexpr int kFinLanes = kThreads / kFinCols;
+
+struct Drop {
+    const float *tab;  // [B x ld] or null
+    long long ld;
+    const int32_t *row_seg;
+};
+
+__device__ __forceinline__ void load_f8(const float *p, float (&v)[8]) {
+    const float4v lo = *reinterpret_cast<const float4v *>(p), hi = *reinterpret_cast<const float4v *>(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        v[e] = lo[e];
+        v[e + 4] = hi[e];
+    }
+}
+
+// the row lanes' sums of a column, added in lane order; part[(2 chunk + k) * D + col]
+__device__ __forceinline__ void reduce_store(double (&s0)[8], double (&s1)[8], double *part, int D) {
+    __shared__ double red[kRowLanes][kSlab];
+    const int cx = threadIdx.x % kColLanes, ry = threadIdx.x / kColLanes;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[ry][cx * 8 + e] = k ? s1[e] : s0[e];
+        __syncthreads();
+        for (int cl = threadIdx.x; cl < kSlab && blockIdx.x * kSlab + cl < D; cl += kThreads) {
+            double t = red[0][cl];
+#pragma unroll
+            for (int y = 1; y < kRowLanes; ++y) t += red[y][cl];
+            part[((long long)blockIdx.y * 2 + k) * D + blockIdx.x * kSlab + cl] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// partials of sum r and sum r^2 (one conversion to double per element; its square is exact there)
+__global__ __launch_bounds__(kThreads) void k_bn_fwd_part(const h16 *r, long long ld, int rows, int D, double *part) {
+    const int cx = threadIdx.x % kColLanes, ry = threadIdx.x / kColLanes;
+    const int c0 = blockIdx.x * kSlab + cx * 8;
+    const int r0 = blockIdx.y * kChunk, r1 = min(rows, r0 + kChunk);
+    double s0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (c0 < D) {
+#pragma unroll 4
+        for (int m = r0 + ry; m < r1; m += kRowLanes) {
+            const half8 v = load_h8(r + (long long)m * ld + c0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const double x = (double)h2f(v[e]);
+                s0[e] += x;
+                s1[e] = fma(x, x, s1[e]);
+            }
+        }
+    }
+    reduce_store(s0, s1, part, D);
+}
+
+// partials of sum dy and sum dy r, dy = g * drop[row_seg[row]] (exact in double)
+template <bool DROP>
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_part(const h16 *g, long long ldg, const h16 *r, long long ldr,
+                                                          int rows, int D, Drop dr, double *part) {
+    const int cx = threadIdx.x % kColLanes, ry = threadIdx.x / kColLanes;
+    const int c0 = blockIdx.x * kSlab + cx * 8;
+    const int r0 = blockIdx.y * kChunk, r1 = min(rows, r0 + kChunk);
+    double s0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (c0 < D) {
+#pragma unroll 2
+        for (int m = r0 + ry; m < r1; m += kRowLanes) {
+            const half8 gv = load_h8(g + (long long)m * ldg + c0);
+            const half8 rv = load_h8(r + (long long)m * ldr + c0);
+            float d[8];
+            if constexpr (DROP) load_f8(dr.tab + (long long)dr.row_seg[m] * dr.ld + c0, d);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                double dy = (double)h2f(gv[e]);
+                if constexpr (DROP) dy *= (double)d[e];
+                s0[e] += dy;
+                s1[e] = fma(dy, (double)h2f(rv[e]), s1[e]);
+            }
+        }
+    }
+    reduce_store(s0, s1, part, D);
+}
+
+// sum and sum of squares of column c over the chunks, in the fixed order above; valid in lane 0
+__device__ __forceinline__ void sum_chunks(const double *part, int nchunk, int D, int c, int lane, double &s, double &q) {
+    __shared__ double red[2][kFinLanes][kFinCols];
+    double s0 = 0.0, q0 = 0.0;
+    if (c < D) {
+#pragma unroll 4
+        for (int k = lane; k < nchunk; k += kFinLanes) {
+            s0 += part[((long long)k * 2) * D + c];
+            q0 += part[((long long)k * 2 + 1) * D + c];
+        }
+    }
+    red[0][lane][threadIdx.x % kFinCols] = s0;
+    red[1][lane][threadIdx.x % kFinCols] = q0;
+    __syncthreads();
+    s = red[0][0][threadIdx.x % kFinCols];
+    q = red[1][0][threadIdx.x % kFinCols];
+    if (lane == 0) {
+#pragma unroll
+        for (int l = 1; l < kFinLanes; ++l) {
+            s += red[0][l][threadIdx.x % kFinCols];
+            q += red[1][l][threadIdx.x % kFinCols];
+        }
+    }
+}
+
+// forward: the chunks in order, then mean, var (floored at 0), scale = rms (var + eps)^-1/2 and
+// shift = -mean scale in double, stored in fp32; the accumulators take the sums as they are
+__global__ __launch_bounds__(kThreads) void k_bn_fwd_finish(const double *part, int nchunk, int rows, int D, double eps,
+                                                            double rms, float *mean, float *var, float *scale,
+                                                            float *shift, double *acc_count, double *acc_sum,
+                                                            double *acc_sumsq) {
+    const int c = blockIdx.x * kFinCols + threadIdx.x % kFinCols, lane = threadIdx.x / kFinCols;
+    double s, q;
+    sum_chunks(part, nchunk, D, c, lane, s, q);
+    if (c >= D || lane != 0) return;
+    const double mu = s / rows;
+    double v = q / rows - mu * mu;
+    v = v > 0.0 ? v : 0.0;
+    const double sc = rms / sqrt(v + eps);
+    mean[c] = (float)mu;
+    var[c] = (float)v;
+    scale[c] = (float)sc;
+    shift[c] = (float)(-mu * sc);
+    if (acc_sum) {
+        acc_sum[c] += s;
+        acc_sumsq[c] += q;
+        if (c == 0) acc_count[0] += (double)rows;
+    }
+}
+
+// backward: a = sum dy / n, b = sum dy yhat / n with yhat = (r scale + shift) / rms, so
+// sum dy yhat = (scale sum dy r + shift sum dy) / rms
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_finish(const double *part, int nchunk, int rows, int D,
+                                                            const float *scale, const float *shift, double inv_rms,
+                                                            float *a, float *b) {
+    const int c = blockIdx.x * kFinCols + threadIdx.x % kFinCols, lane = threadIdx.x / kFinCols;
+    double s, q;
+    sum_chunks(part, nchunk, D, c, lane, s, q);
+    if (c >= D || lane != 0) return;
+    a[c] = (float)(s / rows);
+    b[c] = (float)(((double)scale[c] * q + (double)shift[c] * s) * inv_rms / rows);
+}
+
+// out = rne_fp16(((r scale + shift) drop) + alpha resid): the fused epilogue's fp32 operations in
+// its order (gemm_common.h epilogue8: fmaf, multiply, fmaf). Thread = 8 columns of one row.
+__global__ __launch_bounds__(kThreads) void k_bn_fwd_apply(const h16 *r, long long ld, long long units, int d8,
+                                                           const float *scale, const float *shift, Drop dr,
+                                                           const h16 *resid, long long ldres, float alpha, h16 *out,
+                                                           long long ldo) {
+    const long long u = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (u >= units) return;
+    const long long m = u / d8;
+    const int c0 = (int)(u - m * d8) * 8;
+    const half8 rv = load_h8(r + m * ld + c0);
+    float sc[8], sh[8], v[8];
+    load_f8(scale + c0, sc);
+    load_f8(shift + c0, sh);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = fmaf(h2f(rv[e]), sc[e], sh[e]);
+    if (dr.tab) {
+        float d[8];
+        load_f8(dr.tab + (long long)dr.row_seg[m] * dr.ld + c0, d);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= d[e];
+    }
+    if (resid) {
+        const half8 x = load_h8(resid + m * ldres + c0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = fmaf(alpha, h2f(x[e]), v[e]);
+    }
+    half8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = f2h(v[e]);
+    store_h8(out + m * ldo + c0, o);
+}
+
+// dz = rne_fp16(scale (dy - a - yhat b) relu_bit), in double up to the store. Thread = 8 columns of
+// kApplyRows consecutive rows, so that the columns' constants are made once for them:
+// scale (dy - a - yhat b) = scale dy - k1 r - k0 with k1 = scale^2 b / rms, k0 = scale (a + b shift / rms)
+constexpr int kApplyRows = 4;
+template <bool DROP>
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const h16 *g, long long ldg, const h16 *r, long long ldr,
+                                                           int rows, long long units, int d8, const float *scale,
+                                                           const float *shift, double inv_rms, const float *a,
+                                                           const float *b, Drop dr, const uint8_t *mask,
+                                                           long long ld_mask, h16 *dz, long long lddz) {
+    const long long u = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (u >= units) return;
+    const long long grp = u / d8;
+    const int c0 = (int)(u - grp * d8) * 8;
+    float sc[8], sh[8], av[8], bv[8];
+    load_f8(scale + c0, sc);
+    load_f8(shift + c0, sh);
+    load_f8(a + c0, av);
+    load_f8(b + c0, bv);
+    double scd[8], k1[8], k0[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        scd[e] = (double)sc[e];
+        const double sb = scd[e] * (double)bv[e] * inv_rms;
+        k1[e] = sb * scd[e];
+        k0[e] = fma(sb, (double)sh[e], scd[e] * (double)av[e]);
+    }
+    const long long m0 = grp * kApplyRows;
+#pragma unroll
+    for (int i = 0; i < kApplyRows; ++i) {
+        const long long m = m0 + i;
+        if (m >= rows) break;
+        const half8 gv = load_h8(g + m * ldg + c0), rv = load_h8(r + m * ldr + c0);
+        const unsigned bits = mask[(m * ld_mask + c0) >> 3];
+        float d[8];
+        if constexpr (DROP) load_f8(dr.tab + (long long)dr.row_seg[m] * dr.ld + c0, d);
+        half8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            double dy = (double)h2f(gv[e]);
+            if constexpr (DROP) dy *= (double)d[e];
+            const double w = fma(scd[e], dy, -fma(k1[e], (double)h2f(rv[e]), k0[e]));
+            o[e] = ((bits >> e) & 1u) ? f2h((float)w) : (h16)0.f;
+        }
+        store_h8(dz + m * lddz + c0, o);
+    }
+}
+
+bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// shape rules shared by the four entries: rows x D fp16 tensors read with 16-byte lanes
+bool shape_ok(const char *what, int rows, int D) {
+    if (rows > 0 && rows <= 65535 * kChunk && D > 0 && D % 8 == 0) return true;
+    kf_report_error("%s: needs 0 < rows <= %d, D > 0 and D %% 8 == 0 (rows=%d D=%d)", what, 65535 * kChunk, rows, D);
+    return false;
+}
+bool tensor_ok(const char *what, const char *name, const void *p, long long ld, int D) {
+    if (p && al16(p) && ld >= D && ld % 8 == 0) return true;
+    kf_report_error("%s: %s needs a 16-byte aligned pointer and ld >= D, ld %% 8 == 0 (ld=%lld D=%d)", what, name, ld, D);
+    return false;
+}
+bool cols_ok(const char *what, const char *name, const float *p) {
+    if (p && al16(p)) return true;
+    kf_report_error("%s: %s needs a 16-byte aligned pointer", what, name);
+    return false;
+}
+bool drop_ok(const char *what, const float *drop, long long ld_drop, const int32_t *row_seg, int D) {
+    if (!drop) return true;
+    if (row_seg && al16(drop) && ld_drop >= D && ld_drop % 4 == 0) return true;
+    kf_report_error("%s: drop needs row_seg, a 16-byte aligned table and ld_drop >= D, ld_drop %% 4 == 0", what);
+    return false;
+}
+bool launched(const char *what) {
+    if (hipGetLastError() == hipSuccess) return true;
+    kf_report_error("%s: launch failed", what);
+    return false;
+}
+int chunks_of(int rows) { return (rows + kChunk - 1) / kChunk; }
+double *partials(const char *what, int rows, int D) {
+    double *p = (double *)kf_workspace_stream((size_t)chunks_of(rows) * 2 * D * sizeof(double));
+    if (!p) kf_report_error("%s: workspace", what);
+    return p;
+}
+
+}  // namespace
+
+extern "C" int kf_bn_train_stats(const void *r, long long ld, int rows, int D, float eps, float target_rms, float *mean,
+                                 float *var, float *scale, float *shift, double *acc_count, double *acc_sum,
+                                 double *acc_sumsq) {
+    kf_take_pending(__func__);
+    const char *what = "kf_bn_train_stats";
+    if (!shape_ok(what, rows, D) || !tensor_ok(what, "r", r, ld, D)) return -1;
+    if (!mean || !var || !scale || !shift || !(eps >= 0.f) || !(target_rms > 0.f) ||
+        ((acc_count || acc_sum || acc_sumsq) && !(acc_count && acc_sum && acc_sumsq))) {
+        kf_report_error("%s: needs mean, var, scale, shift, eps >= 0, target_rms > 0 and all three accumulators or none", what);
+        return -1;
+    }
+    double *part = partials(what, rows, D);
+    if (!part) return -1;
+    const int nchunk = chunks_of(rows);
+    const dim3 grid((unsigned)((D + kSlab - 1) / kSlab), (unsigned)nchunk);
+    k_bn_fwd_part<<<grid, kThreads, 0, kf_stream()>>>((const h16 *)r, ld, rows, D, part);
+    k_bn_fwd_finish<<<(unsigned)((D + kFinCols - 1) / kFinCols), kThreads, 0, kf_stream()>>>(
+        part, nchunk, rows, D, (double)eps, (double)target_rms, mean, var, scale, shift, acc_count, acc_sum, acc_sumsq);
+    return launched(what) ? 0 : -1;
+}
+
+extern "C" int kf_bn_train_apply(const void *r, long long ld, int rows, int D, const float *scale, const float *shift,
+                                 const float *drop, long long ld_drop, const int32_t *row_seg, const void *resid,
+                                 long long ldr, float alpha, void *out, long long ldo) {
+    kf_take_pending(__func__);
+    const char *what = "kf_bn_train_apply";
+    if (!shape_ok(what, rows, D) || !tensor_ok(what, "r", r, ld, D) || !tensor_ok(what, "out", out, ldo, D) ||
+        !cols_ok(what, "scale", scale) || !cols_ok(what, "shift", shift) || !drop_ok(what, drop, ld_drop, row_seg, D) ||
+        (resid && !tensor_ok(what, "resid", resid, ldr, D)))
+        return -1;
+    const int d8 = D / 8;
+    const long long units = (long long)rows * d8;
+    k_bn_fwd_apply<<<(unsigned)((units + kThreads - 1) / kThreads), kThreads, 0, kf_stream()>>>(
+        (const h16 *)r, ld, units, d8, scale, shift, Drop{drop, ld_drop, row_seg}, (const h16 *)resid, ldr, alpha,
+        (h16 *)out, ldo);
+    return launched(what) ? 0 : -1;
+}
+
+extern "C" int kf_bn_train_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                                     const float *scale, const float *shift, float target_rms, const float *drop,
+                                     long long ld_drop, const int32_t *row_seg, float *a, float *b) {
+    kf_take_pending(__func__);
+    const char *what = "kf_bn_train_bwd_stats";
+    if (!shape_ok(what, rows, D) || !tensor_ok(what, "g", g, ldg, D) || !tensor_ok(what, "r", r, ldr, D) ||
+        !drop_ok(what, drop, ld_drop, row_seg, D))
+        return -1;
+    if (!scale || !shift || !a || !b || !(target_rms > 0.f)) {
+        kf_report_error("%s: needs scale, shift, a, b and target_rms > 0", what);
+        return -1;
+    }
+    double *part = partials(what, rows, D);
+    if (!part) return -1;
+    const int nchunk = chunks_of(rows);
+    const dim3 grid((unsigned)((D + kSlab - 1) / kSlab), (unsigned)nchunk);
+    const Drop dr{drop, ld_drop, row_seg};
+    if (drop) k_bn_bwd_part<true><<<grid, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, D, dr, part);
+    else k_bn_bwd_part<false><<<grid, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, D, dr, part);
+    k_bn_bwd_finish<<<(unsigned)((D + kFinCols - 1) / kFinCols), kThreads, 0, kf_stream()>>>(
+        part, nchunk, rows, D, scale, shift, 1.0 / (double)target_rms, a, b);
+    return launched(what) ? 0 : -1;
+}
+
+extern "C" int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                                     const float *scale, const float *shift, float target_rms, const float *a,
+                                     const float *b, const float *drop, long long ld_drop, const int32_t *row_seg,
+                                     const uint8_t *mask, long long ld_mask, void *dz, long long lddz) {
+    kf_take_pending(__func__);
+    const char *what = "kf_bn_train_bwd_apply";
+    if (!shape_ok(what, rows, D) || !tensor_ok(what, "g", g, ldg, D) || !tensor_ok(what, "r", r, ldr, D) ||
+        !tensor_ok(what, "dz", dz, lddz, D) || !cols_ok(what, "scale", scale) || !cols_ok(what, "shift", shift) ||
+        !cols_ok(what, "a", a) || !cols_ok(what, "b", b) || !drop_ok(what, drop, ld_drop, row_seg, D))
+        return -1;
+    if (!mask || ld_mask < D || ld_mask % 8 || !(target_rms > 0.f)) {
+        kf_report_error("%s: needs the ReLU mask with ld_mask >= D bits, ld_mask %% 8 == 0, and target_rms > 0", what);
+        return -1;
+    }
+    const int d8 = D / 8;
+    const long long units = (long long)((rows + kApplyRows - 1) / kApplyRows) * d8;
+    const unsigned nblk = (unsigned)((units + kThreads - 1) / kThreads);
+    const Drop dr{drop, ld_drop, row_seg};
+    const double inv_rms = 1.0 / (double)target_rms;
+    if (drop)
+        k_bn_bwd_apply<true><<<nblk, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, units, d8, scale,
+                                                                shift, inv_rms, a, b, dr, mask, ld_mask, (h16 *)dz, lddz);
+    else
+        k_bn_bwd_apply<false><<<nblk, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, units, d8, scale,
+                                                                 shift, inv_rms, a, b, dr, mask, ld_mask, (h16 *)dz, lddz);
+    return launched(what) ? 0 : -1;
+}

@@ -33,6 +33,16 @@ bool dx_epilogue(KfNet *net, int P, void *dz_out, void *g_out, KfEpilogue &E, bo
     if (di >= 0) net->dz_imp[di] = net->dz_edge[di] = false;
     switch (L.type) {
         case LayerType::TDNNF: {
+            if (pl.bnt_act) {
+                // training-mode BatchNorm: the raw g only, bypass or not (the g ring
+                // is as wide as the widest layer); P's own step turns it into dz, through the
+                // batch statistics (BackwardPass::tdnnf). dz_edge stays false: that step's
+                // kf_rows_sum_mask sums the strided layers' edge row.
+                E.out = g_out;
+                E.ldo = w;
+                E.out2 = nullptr;
+                return true;
+            }
             E.scale2 = pl.bn_scale;
             E.mask_in = pl.mask;
             if (pl.drop_act) {
@@ -281,6 +291,7 @@ struct BackwardPass {
     bool to_full_epilogue(Step &s), to_full_scatter(Step &s);
     bool linear(Step &s), attention(Step &s), prefinal(Step &s), combine(Step &s), tdnnf(Step &s), conv(Step &s);
     KfOperand masked(const Step &s, const Tdnnf &t, KfOperand o) const;
+    bool bn_train_dz(Step &s, int ib);
     bool tdnnf_affine_wgrad(Step &s, const Tdnnf &t), tdnnf_affine_dgrad(Step &s, const Tdnnf &t);
     bool tdnnf_affine_dgrad_mx(Step &s, const Tdnnf &t, const KfEpilogue &E1, void *edge);
     bool tdnnf_linear_wgrad(Step &s, const Tdnnf &t), tdnnf_linear_dgrad(Step &s, const Tdnnf &t);
@@ -649,6 +660,11 @@ bool BackwardPass::tdnnf(Step &s) {
     const int st = nl.compact && net->rs.Tc ? L.time_stride / 3 : L.time_stride, np = st > 0 ? 2 : 1;
     const int ib = dz_index(net, dz);
     const bool imp = ib >= 0 && net->dz_imp[ib];
+    // training-mode BatchNorm: the layer above left the raw g (dx_epilogue); a, b over
+    // the layer's rows, then dz into the ring buffer its epilogue left unwritten, on the chain
+    // stream. Every consumer below, the weight-gradient stream's included (wgrad() orders it
+    // behind what the chain enqueued), reads dz as from a frozen layer.
+    if (nl.bnt_act && !bn_train_dz(s, ib)) return false;
     Tdnnf t{st, L.bottleneck, np * L.in_dim, np * L.bottleneck, ib, imp, imp ? gcur : dz, nullptr, nullptr};
     // The affine weight gradients run on the weight-gradient stream. (r5, with a
     // two-deep gradient ring, every other one ran on the chain: the chain waited for
@@ -670,6 +686,27 @@ bool BackwardPass::tdnnf(Step &s) {
     if (!tdnnf_affine_dgrad(s, t) || (aff_on_main && !tdnnf_affine_wgrad(s, t))) return false;
     if (!wgrad([&] { return tdnnf_linear_wgrad(s, t); })) return false;
     return !s.want_dx || (dx_wait() && tdnnf_linear_dgrad(s, t));
+}
+
+#pragma weak kf_bn_train_bwd_stats
+#pragma weak kf_bn_train_bwd_apply
+
+bool BackwardPass::bn_train_dz(Step &s, int ib) {
+    NetLayer &nl = s.nl;
+    const int T = s.T, D = nl.L.out_dim;
+    if (ib < 0 || gcur == dz || D > net->bnt_w || !kf_bn_train_bwd_stats || !kf_bn_train_bwd_apply) {
+        set_err("backward: training-mode BatchNorm of " + nl.L.name + " got no stored output gradient");
+        return false;
+    }
+    const float *sc = nl.bnt_stat + 2 * D, *sh = nl.bnt_stat + 3 * D;
+    const float *drop = nl.drop_act ? nl.drop : nullptr;
+    const int32_t *rseg = drop ? drop_rows(net, nl.compact) : nullptr;
+    float *a = net->bnt_ab, *b = net->bnt_ab + net->bnt_w;
+    return ck(kf_bn_train_bwd_stats(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, drop, D, rseg, a, b),
+              "tdnnf batchnorm backward statistics") &&
+           ck(kf_bn_train_bwd_apply(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
+                                    net->dz[ib], D),
+              "tdnnf batchnorm backward apply");
 }
 
 KfOperand BackwardPass::masked(const Step &s, const Tdnnf &t, KfOperand o) const {
@@ -1060,6 +1097,10 @@ extern "C" int nnet_backward_n(KfNet *net, const void *out_grad, int n) {
     }
     if (net && drop_active(net)) {
         set_err("backward_n: not supported with dropout on (nnet_set_dropout)");
+        return -1;
+    }
+    if (net && bnt_active(net)) {
+        set_err("backward_n: not supported with training-mode BatchNorm on (nnet_set_bn_train)");
         return -1;
     }
     return backward_impl(net, out_grad, n);

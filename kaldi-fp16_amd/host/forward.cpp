@@ -183,7 +183,20 @@ bool fwd_tdnnf(KfNet *net, int li, const void *x) {
         E2.ld_drop = dout;
         E2.row_seg = drop_rows(net, nl.compact);
     }
-    return ck(kf_gemm_fused(T, dout, f8b ? nl.w8b.ld : kaff, &A2, &B2, &E2), "tdnnf affine");
+    if (!nl.bnt_act) return ck(kf_gemm_fused(T, dout, f8b ? nl.w8b.ld : kaff, &A2, &B2, &E2), "tdnnf affine");
+    // training-mode BatchNorm: the GEMM writes r = relu(affine + bias) and the mask
+    // only; the batch statistics of r, then the epilogue's scale / shift / dropout / bypass on them
+    KfEpilogue Er = epi_relu_bn(net, nl, nl.pb2, dout);
+    Er.out = nl.bnt_r;
+    Er.scale = Er.shift = nullptr;
+    float *const st = nl.bnt_stat;
+    return ck(kf_gemm_fused(T, dout, kaff, &A2, &B2, &Er), "tdnnf affine") &&
+           ck(kf_bn_train_stats(nl.bnt_r, dout, T, dout, nl.bn_eps, nl.bn_rms, st, st + dout, st + 2 * dout, st + 3 * dout,
+                                nl.bnt_acc, nl.bnt_acc + 2, nl.bnt_acc + 2 + dout),
+              "tdnnf batchnorm statistics") &&
+           ck(kf_bn_train_apply(nl.bnt_r, dout, T, dout, st + 2 * dout, st + 3 * dout, E2.drop, E2.ld_drop, E2.row_seg,
+                                E2.resid, E2.ldr, E2.resid_alpha, nl.act, dout),
+              "tdnnf batchnorm apply");
 }
 
 // a plain x . W layer (linear, output): MXFP8 when the input has a copy
@@ -395,6 +408,24 @@ bool sa_prepare(KfNet *net) {
     return true;
 }
 
+#pragma weak kf_bn_train_stats
+#pragma weak kf_bn_train_apply
+
+// Training-mode BatchNorm of this forward: every governed layer normalises by its
+// own batch statistics while the switch is on. The switches refuse the combinations below when
+// they are set (network.cpp); this is the same rule where the forward would break it.
+bool bnt_prepare(KfNet *net) {
+    for (int li : net->bnt_layers) net->layers[li].bnt_act = false;
+    if (!bnt_active(net)) return true;
+    if (net->fp8 || net->implicit_dz || net->rs.Tc > 0 || net->dp || !kf_bn_train_stats || !kf_bn_train_apply) {
+        set_err("forward: training-mode BatchNorm is not supported in MXFP8 mode, with implicit dz, row subsampling or "
+                "a data-parallel communicator");
+        return false;
+    }
+    for (int li : net->bnt_layers) net->layers[li].bnt_act = net->layers[li].bnt_r != nullptr;
+    return true;
+}
+
 int forward_impl(KfNet *net, const void *features, int T) {
     if (!on_device(net, "forward")) return -1;
     if (!refresh_wt(net)) return -1;
@@ -410,7 +441,7 @@ int forward_impl(KfNet *net, const void *features, int T) {
         const int tc0 = (T - 1) / 3 + 1;
         if (tc0 >= 4 * nt + 16 && tc0 + nt <= net->maxTc) net->rs = RowSet(T, tc0, nt);
     }
-    if (!drop_prepare(net) || !sa_prepare(net)) return -1;
+    if (!drop_prepare(net) || !sa_prepare(net) || !bnt_prepare(net)) return -1;
     for (size_t li = 0; li < net->layers.size(); ++li) {
         NetLayer &nl = net->layers[li];
         const void *x = act_of(net, nl.input);

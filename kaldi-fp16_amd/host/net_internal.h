@@ -87,6 +87,15 @@ struct NetLayer {
     int drop_ord = -1;
     float *drop = nullptr;
     bool drop_act = false;
+    // training-mode BatchNorm (TDNN-F, kf_nnet.h nnet_set_bn_train): r = the affine's
+    // relu output fp16 [max_T x out_dim], the last forward's mean | var | scale | shift (fp32, out_dim
+    // each; bn_scale / bn_shift stay the frozen pair), the accumulators count (2 doubles, the
+    // second unused) | sum | sumsq in double, all made when the mode is first switched on, and
+    // whether the current forward normalised by its own statistics
+    void *bnt_r = nullptr;
+    float *bnt_stat = nullptr;
+    double *bnt_acc = nullptr;
+    bool bnt_act = false;
     // spec-augment-layer (kf_nnet.h nnet_set_spec_augment): the layer's ordinal among such layers
     // (-1: another kind), its options, the row_band [max_T] of its last active forward, and
     // whether the current forward masked (act is then the layer's own buffer, not the alias)
@@ -261,6 +270,13 @@ struct KfNet {
     int sa_on = 0;
     unsigned long long sa_seed = 0;
     long long sa_step = 0;
+    // training-mode BatchNorm (kf_nnet.h nnet_set_bn_train): the layers the switch
+    // governs (the tdnnf-layers), the switch, and the backward's a | b columns (fp32, the widest
+    // governed layer's out_dim each; one pair: the chain stream runs the layers in order)
+    std::vector<int> bnt_layers;
+    int bnt_on = 0;
+    float *bnt_ab = nullptr;
+    int bnt_w = 0;
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]
@@ -401,6 +417,8 @@ inline int att_affine(const Layer &L) {
 inline bool drop_active(const KfNet *net) { return net->drop_on && !net->drop_layers.empty(); }
 // SpecAugment is switched on and the network has a spec-augment layer (nnet_set_spec_augment)
 inline bool sa_active(const KfNet *net) { return net->sa_on && !net->sa_layers.empty(); }
+// training-mode BatchNorm is switched on and the network has a layer it governs (nnet_set_bn_train)
+inline bool bnt_active(const KfNet *net) { return net->bnt_on && !net->bnt_layers.empty(); }
 // Z = min(D, floor(D f + 0.5)): the widest band of a spec-augment layer
 inline int sa_max_bins(const NetLayer &nl) {
     return std::min(nl.L.out_dim, (int)((double)nl.L.out_dim * nl.sa_f + 0.5));

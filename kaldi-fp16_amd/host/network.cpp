@@ -307,6 +307,7 @@ static bool build_topology(KfNet *net, const char *xconfig_text, int max_frames,
                 nl.pb2 = add_param(net, n + ".AffineBias", 1, dout);
                 nl.bypass = L.bypass_scale > 0 && din == dout;
                 identity_bn(nl.hbn, dout);
+                net->bnt_layers.push_back((int)net->layers.size());  // (nnet_set_bn_train governs it)
                 if (L.dropout_proportion >= 0) {  // the layer has a dropout component
                     nl.drop_p = (float)L.dropout_proportion;
                     nl.drop_ord = (int)net->drop_layers.size();
@@ -885,6 +886,10 @@ extern "C" int nnet_set_fp8(KfNet *net, int on) {
         set_err("set_fp8: not supported with dropout on (nnet_set_dropout)");
         return -1;
     }
+    if (bnt_active(net)) {
+        set_err("set_fp8: not supported with training-mode BatchNorm on (nnet_set_bn_train)");
+        return -1;
+    }
     if (sa_active(net) && !sa_mx_conflict(net).empty()) {
         set_err("set_fp8: with SpecAugment on (nnet_set_spec_augment) layer " + sa_mx_conflict(net) +
                 " would read the unmasked MXFP8 copy of a spec-augment layer's input");
@@ -929,6 +934,10 @@ extern "C" int nnet_set_implicit_dz(KfNet *net, int on) {
         set_err("set_implicit_dz: not supported with dropout on (nnet_set_dropout)");
         return -1;
     }
+    if (on && bnt_active(net)) {
+        set_err("set_implicit_dz: not supported with training-mode BatchNorm on (nnet_set_bn_train)");
+        return -1;
+    }
     net->implicit_dz = on != 0;
     return 0;
 }
@@ -941,6 +950,10 @@ extern "C" int nnet_set_row_subsampling(KfNet *net, int stride) {
     }
     if (stride != 3) {
         set_err("set_row_subsampling: stride " + std::to_string(stride) + " (only 3: chain frame subsampling)");
+        return -1;
+    }
+    if (bnt_active(net)) {
+        set_err("set_row_subsampling: not supported with training-mode BatchNorm on (nnet_set_bn_train)");
         return -1;
     }
     // the top of the output chain whose rows are row-local or 3-strided: TDNN-F with time
@@ -1656,6 +1669,11 @@ extern "C" int nnet_bind_dp(KfNet *net, KfDp *dp, long long bucket_bytes) {
         set_err("bind_dp: not supported with natural gradient on (nnet_set_natural_gradient)");
         return -1;
     }
+    if (bnt_active(net)) {
+        set_err("bind_dp: not supported with training-mode BatchNorm on (nnet_set_bn_train): the statistics "
+                "would be each rank's own");
+        return -1;
+    }
     std::vector<int> after(256);
     std::vector<long long> b(256), e(256);
     const int nb = nnet_dp_plan(net, bucket_bytes, 256, after.data(), b.data(), e.data());
@@ -1896,4 +1914,160 @@ extern "C" int nnet_spec_augment_rows(KfNet *net, const char *layer, int32_t *ho
         return -1;
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Training-mode BatchNorm of the TDNN-F layers (kf_nnet.h nnet_set_bn_train): the
+// switch, the statistics and the commit. forward.cpp normalises by the batch statistics,
+// backward.cpp differentiates through them.
+// ---------------------------------------------------------------------------
+#pragma weak kf_bn_train_stats
+
+static NetLayer *bnt_layer(KfNet *net, const char *layer, int which, const char *what) {
+    if (net && layer)
+        for (int li : net->bnt_layers)
+            if (net->layers[li].L.name == layer && which == 0) return &net->layers[li];
+    set_err(std::string(what) + ": training-mode BatchNorm (nnet_set_bn_train) does not govern BatchNorm '" +
+            std::to_string(which) + "' of layer " + (layer ? layer : "(null)"));
+    return nullptr;
+}
+
+extern "C" int nnet_bn_train_layers(const KfNet *net, int *idx, int n) {
+    if (!net) return -1;
+    for (int i = 0; idx && i < n && i < (int)net->bnt_layers.size(); ++i) idx[i] = net->bnt_layers[i];
+    return (int)net->bnt_layers.size();
+}
+
+extern "C" int nnet_set_bn_train(KfNet *net, int on) {
+    if (!on_device(net, "set_bn_train")) return -1;
+    if (!on || net->bnt_layers.empty()) {
+        net->bnt_on = on != 0;
+        return 0;
+    }
+    if (net->fp8) {
+        set_err("set_bn_train: not supported in MXFP8 mode (nnet_set_fp8)");
+        return -1;
+    }
+    if (net->implicit_dz) {
+        set_err("set_bn_train: not supported with implicit dz (nnet_set_implicit_dz)");
+        return -1;
+    }
+    if (net->rsub) {
+        // (the compact row set's scratch row and inexact tail rows are not rows of the layer)
+        set_err("set_bn_train: not supported with row subsampling (nnet_set_row_subsampling)");
+        return -1;
+    }
+    if (net->dp) {
+        set_err("set_bn_train: not supported with a data-parallel communicator bound (nnet_bind_dp): the statistics "
+                "would be each rank's own");
+        return -1;
+    }
+    if (!kf_bn_train_stats) {
+        set_err("set_bn_train: this build of libkaldi_fp16 has no training-mode BatchNorm kernels");
+        return -1;
+    }
+    int maxw = 0;
+    for (int li : net->bnt_layers) maxw = std::max(maxw, net->layers[li].L.out_dim);
+    if (!net->bnt_ab) {  // the first time: r, the batch statistics and the accumulators of every layer
+        for (int li : net->bnt_layers) {
+            NetLayer &nl = net->layers[li];
+            const size_t D = (size_t)nl.L.out_dim;
+            if (D % 8 || !nl.mask) {
+                set_err("set_bn_train: layer " + nl.L.name + " needs out_dim % 8 == 0 and a ReLU mask");
+                return -1;
+            }
+            nl.bnt_r = net->dalloc((size_t)net->max_T * D * 2);
+            nl.bnt_stat = (float *)net->dalloc(4 * D * 4);
+            nl.bnt_acc = (double *)net->dalloc((2 + 2 * D) * 8);
+            if (!nl.bnt_r || !nl.bnt_stat || !nl.bnt_acc) {
+                set_err("set_bn_train: alloc " + nl.L.name);
+                return -1;
+            }
+            bridge_gpu_memset(nl.bnt_stat, 0, 4 * D * 4);
+            bridge_gpu_memset(nl.bnt_acc, 0, (2 + 2 * D) * 8);
+        }
+        if (!(net->bnt_ab = (float *)net->dalloc((size_t)2 * maxw * 4))) {
+            set_err("set_bn_train: alloc backward columns");
+            return -1;
+        }
+        net->bnt_w = maxw;
+    }
+    net->bnt_on = 1;
+    return 0;
+}
+
+extern "C" int nnet_bn_batch_stats(KfNet *net, const char *layer, int which, float *mean, float *var) {
+    if (!on_device(net, "bn_batch_stats")) return -1;
+    NetLayer *nl = bnt_layer(net, layer, which, "bn_batch_stats");
+    if (!nl) return -1;
+    if (!nl->bnt_act || !nl->bnt_stat) {
+        set_err(std::string("bn_batch_stats: the last forward did not run ") + layer + " in training mode");
+        return -1;
+    }
+    const size_t D = (size_t)nl->L.out_dim;
+    // (ordered behind the forward on the current stream, and synchronises; fp32 read = 2x fp16 count)
+    if ((mean && bridge_read_fp16((uint16_t *)mean, nl->bnt_stat, 2 * D)) ||
+        (var && bridge_read_fp16((uint16_t *)var, nl->bnt_stat + D, 2 * D))) {
+        set_err("bn_batch_stats: read");
+        return -1;
+    }
+    return 0;
+}
+
+// (ordered behind the forward on the current stream, and synchronises; a double read = 4x fp16 count)
+static bool bnt_read_acc(NetLayer &nl, std::vector<double> &h) {
+    h.assign(2 + 2 * (size_t)nl.L.out_dim, 0.0);
+    return !nl.bnt_acc || bridge_read_fp16((uint16_t *)h.data(), nl.bnt_acc, h.size() * 4) == 0;
+}
+
+extern "C" int nnet_bn_stats(KfNet *net, const char *layer, int which, double *count, double *sum, double *sumsq) {
+    if (!on_device(net, "bn_stats")) return -1;
+    NetLayer *nl = bnt_layer(net, layer, which, "bn_stats");
+    if (!nl) return -1;
+    std::vector<double> h;
+    if (!bnt_read_acc(*nl, h)) {
+        set_err("bn_stats: read");
+        return -1;
+    }
+    const size_t D = (size_t)nl->L.out_dim;
+    if (count) *count = h[0];
+    if (sum) std::copy(h.begin() + 2, h.begin() + 2 + D, sum);
+    if (sumsq) std::copy(h.begin() + 2 + D, h.end(), sumsq);
+    return 0;
+}
+
+extern "C" int nnet_bn_zero_stats(KfNet *net) {
+    if (!on_device(net, "bn_zero_stats")) return -1;
+    for (int li : net->bnt_layers) {
+        NetLayer &nl = net->layers[li];
+        if (nl.bnt_acc) bridge_gpu_memset(nl.bnt_acc, 0, (2 + 2 * (size_t)nl.L.out_dim) * 8);
+    }
+    return 0;
+}
+
+extern "C" int nnet_bn_commit(KfNet *net) {
+    if (!on_device(net, "bn_commit")) return -1;
+    int n = 0;
+    std::vector<double> h;
+    for (int li : net->bnt_layers) {
+        NetLayer &nl = net->layers[li];
+        if (!nl.bnt_acc) continue;
+        if (!bnt_read_acc(nl, h)) {
+            set_err("bn_commit: read");
+            return -1;
+        }
+        if (!(h[0] > 0.0)) continue;
+        const size_t D = (size_t)nl.L.out_dim;
+        std::vector<float> mean(D), var(D), gamma(D, 1.f), beta(D, 0.f);
+        for (size_t c = 0; c < D; ++c) {
+            const double mu = h[2 + c] / h[0], v = h[2 + D + c] / h[0] - mu * mu;
+            mean[c] = (float)mu;
+            var[c] = (float)(v > 0.0 ? v : 0.0);
+        }
+        if (nnet_set_bn(net, nl.L.name.c_str(), 0, mean.data(), var.data(), gamma.data(), beta.data(), nl.bn_eps,
+                        nl.bn_rms) != 0)
+            return -1;
+        ++n;
+    }
+    return n;
 }

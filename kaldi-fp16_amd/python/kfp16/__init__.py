@@ -187,6 +187,13 @@ _sig(nnet, "nnet_set_spec_augment", _i, _vp, _i, C.c_uint64)
 _sig(nnet, "nnet_set_spec_augment_step", _i, _vp, _ll)
 _sig(nnet, "nnet_spec_augment_step", _ll, _vp)
 _sig(nnet, "nnet_spec_augment_rows", _i, _vp, C.c_char_p, _vp, C.POINTER(_i))
+# training-mode BatchNorm (kf_nnet.h nnet_set_bn_train)
+_sig(nnet, "nnet_set_bn_train", _i, _vp, _i)
+_sig(nnet, "nnet_bn_train_layers", _i, _vp, C.POINTER(_i), _i)
+_sig(nnet, "nnet_bn_batch_stats", _i, _vp, C.c_char_p, _i, _vp, _vp)
+_sig(nnet, "nnet_bn_stats", _i, _vp, C.c_char_p, _i, C.POINTER(C.c_double), _vp, _vp)
+_sig(nnet, "nnet_bn_zero_stats", _i, _vp)
+_sig(nnet, "nnet_bn_commit", _i, _vp)
 # kf_dp.h (RCCL data parallel)
 _sig(core, "kf_dp_last_error", C.c_char_p)
 _sig(core, "kf_dp_unique_id", _i, C.c_char_p)
@@ -727,6 +734,54 @@ class Network:
         check(nnet.nnet_spec_augment_rows(self.h, layer.encode(), rows.ctypes.data, None), "nnet_spec_augment_rows")
         return rows
 
+    # training-mode BatchNorm (kf_nnet.h nnet_set_bn_train) -----
+    def set_batchnorm_train(self, on: bool):
+        """Kaldi's training-mode BatchNorm on / off (default off) for the layers
+        batchnorm_train_layers() names: batch statistics in the forward, the exact derivative in
+        the backward, and the count / sum / sumsq accumulators. The frozen statistics are kept."""
+        check(nnet.nnet_set_bn_train(self.h, int(on)), "nnet_set_bn_train")
+
+    def batchnorm_train_layers(self) -> list:
+        """Names of the layers whose BatchNorm the switch governs (today the tdnnf-layers)."""
+        n = nnet.nnet_bn_train_layers(self.h, None, 0)
+        idx = (_i * max(n, 1))()
+        nnet.nnet_bn_train_layers(self.h, idx, n)
+        return [self.layers[idx[i]][0] for i in range(n)]
+
+    def _bn_dim(self, layer: str) -> int:
+        for name, *_rest, dim in self.layers:
+            if name == layer:
+                return dim
+        raise KfError(f"no layer {layer}")
+
+    def batchnorm_batch_stats(self, layer: str, which: int = 0):
+        """(mean, var) float32 [dim] of the last train-mode forward of `layer` (synchronises)."""
+        d = self._bn_dim(layer)
+        mean, var = np.empty(d, np.float32), np.empty(d, np.float32)
+        check(nnet.nnet_bn_batch_stats(self.h, layer.encode(), int(which), mean.ctypes.data, var.ctypes.data),
+              "nnet_bn_batch_stats")
+        return mean, var
+
+    def batchnorm_stats(self, layer: str, which: int = 0):
+        """(count, sum, sumsq): the float64 accumulators of `layer` (synchronises)."""
+        d = self._bn_dim(layer)
+        cnt, s, q = C.c_double(), np.empty(d, np.float64), np.empty(d, np.float64)
+        check(nnet.nnet_bn_stats(self.h, layer.encode(), int(which), C.byref(cnt), s.ctypes.data, q.ctypes.data),
+              "nnet_bn_stats")
+        return cnt.value, s, q
+
+    def batchnorm_zero_stats(self):
+        """Kaldi's ZeroComponentStats for the training-mode BatchNorms."""
+        check(nnet.nnet_bn_zero_stats(self.h), "nnet_bn_zero_stats")
+
+    def batchnorm_commit(self) -> int:
+        """The accumulated statistics become the frozen ones of every governed layer with
+        count > 0 (through nnet_set_bn; eps and target_rms kept); returns the layers committed."""
+        n = nnet.nnet_bn_commit(self.h)
+        if n < 0:
+            check(-1, "nnet_bn_commit")
+        return n
+
     def dp_debug_early(self, on: bool):
         """Test hook: issue every gradient bucket before the backward runs (the
         negative control of the overlap tests)."""
@@ -905,6 +960,11 @@ class KfDropLayer(C.Structure):
 
 _sig(core, "kf_dropout_masks", _i, _i, _vp, _i, C.c_uint64, _ll)
 _sig(core, "kf_row_seg", _i, _vp, _vp, _i, _i, _i, _i)
+_sig(core, "kf_bn_train_stats", _i, _vp, _ll, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig(core, "kf_bn_train_apply", _i, _vp, _ll, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _ll, _f, _vp, _ll)
+_sig(core, "kf_bn_train_bwd_stats", _i, _vp, _ll, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _ll, _vp, _vp, _vp)
+_sig(core, "kf_bn_train_bwd_apply", _i, _vp, _ll, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _ll, _vp, _vp, _ll,
+     _vp, _ll)
 _sig(core, "kf_specaug_rows", _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint64, _ll)
 _sig(core, "kf_specaug_apply", _i, _vp, _ll, _vp, _ll, _ll, _i, _vp)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)

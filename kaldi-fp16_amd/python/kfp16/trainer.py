@@ -17,6 +17,9 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
                                      dropout, one mask row per eg
   1b. (TrainConfig.spec_augment)     -> Network.set_spec_augment: Kaldi's SpecAugment on the
                                      spec-augment-layers, one band and one time mask per eg
+  1c. (TrainConfig.batchnorm_train)  -> Network.set_batchnorm_train: Kaldi's training-mode BatchNorm
+                                     on the TDNN-F layers (batch statistics, exact backward, the
+                                     accumulators commit_batchnorm() later freezes)
   5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
                                      ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
@@ -79,6 +82,11 @@ class TrainConfig:
     # (under data parallel each rank folds its rank in, as for dropout). False: nothing is called.
     spec_augment: bool = False
     spec_augment_seed: int = 0
+    # batchnorm_train: Network.set_batchnorm_train at construction: the TDNN-F layers'
+    # BatchNorm normalises each minibatch by its own statistics, the backward differentiates
+    # through them, and the accumulators start from zero (Kaldi's ZeroComponentStats);
+    # EgsTrainer.commit_batchnorm() makes them the frozen statistics. False: frozen, as before.
+    batchnorm_train: bool = False
 
 
 def parse_dropout_schedule(schedule: str):
@@ -167,6 +175,9 @@ class EgsTrainer:
             self.net.set_dropout(True, (int(self.cfg.dropout_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
         if self.cfg.spec_augment:
             self.net.set_spec_augment(True, (int(self.cfg.spec_augment_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
+        if self.cfg.batchnorm_train:
+            self.net.set_batchnorm_train(True)
+            self.net.batchnorm_zero_stats()
 
     def step(self, batch, allreduce=None, fraction: float | None = None):
         """One TrainStep on `batch` (kfp16.egs.TrainingBatch). allreduce: optional callable
@@ -219,3 +230,9 @@ class EgsTrainer:
     def result(self):
         sync()
         return self.objective.result()
+
+    def commit_batchnorm(self) -> int:
+        """Network.batchnorm_commit: the accumulated statistics of the training-mode BatchNorms
+        become the frozen ones (what a model written after this job carries); returns the number
+        of layers committed. The mode stays as it is."""
+        return self.net.batchnorm_commit()
