@@ -300,13 +300,6 @@ struct BackwardPass {
     bool conv_dgrad_compact(Step &s), conv_dgrad_strided(Step &s), conv_dgrad_plain(Step &s);
 };
 
-// weak, as network.cpp's: a host layer linked against a backend without the kf_ng_* kernels
-// (the launch-trace stub) never gets past nnet_set_natural_gradient
-#pragma weak kf_ng_trx
-#pragma weak kf_ng_scales
-#pragma weak kf_ng_apply
-#pragma weak kf_ng_state
-
 // One side's statistics of a minibatch X [T x D] (kf_ops.h): trX and N, H = X W^T in fp16 (the
 // bias epilogue adds the ones column's term), L = H^T H, and on an updating step JT = X^T H
 // (its bias row: the ones column's). H is one buffer: the stream is in order.
@@ -687,9 +680,6 @@ bool BackwardPass::tdnnf(Step &s) {
     if (!wgrad([&] { return tdnnf_linear_wgrad(s, t); })) return false;
     return !s.want_dx || (dx_wait() && tdnnf_linear_dgrad(s, t));
 }
-
-#pragma weak kf_bn_train_bwd_stats
-#pragma weak kf_bn_train_bwd_apply
 
 bool BackwardPass::bn_train_dz(Step &s, int ib) {
     NetLayer &nl = s.nl;
@@ -1091,18 +1081,7 @@ extern "C" int nnet_backward(KfNet *net, const void *out_grad) {
 }
 // debugging / tests: back-propagate through the top `n` layers only
 extern "C" int nnet_backward_n(KfNet *net, const void *out_grad, int n) {
-    if (net && net->ng_on) {
-        set_err("backward_n: not supported with natural gradient on");
-        return -1;
-    }
-    if (net && drop_active(net)) {
-        set_err("backward_n: not supported with dropout on (nnet_set_dropout)");
-        return -1;
-    }
-    if (net && bnt_active(net)) {
-        set_err("backward_n: not supported with training-mode BatchNorm on (nnet_set_bn_train)");
-        return -1;
-    }
+    if (net && !admit(net, Mode::BackwardN, "backward_n")) return -1;
     return backward_impl(net, out_grad, n);
 }
 // debugging / tests: device pointers of internal tensors

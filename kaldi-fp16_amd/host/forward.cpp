@@ -296,11 +296,6 @@ bool fwd_layer(KfNet *net, int li, const void *x, int T) {
     }
 }
 
-// weak, as network.cpp's: a host layer linked against a backend without the dropout kernels
-// never draws a mask
-#pragma weak kf_dropout_masks
-#pragma weak kf_row_seg
-
 // Per-sequence dropout of this forward: the masks of every layer with a
 // proportion > 0 in one launch, and the row -> sequence maps of the forward's row sets. The
 // step advances at every forward while the switch is on, masks drawn or not. Storage is made
@@ -310,10 +305,7 @@ bool drop_prepare(KfNet *net) {
     net->drop_live = false;
     for (int li : net->drop_layers) net->layers[li].drop_act = false;
     if (!drop_active(net)) return true;
-    if (net->fp8 || net->implicit_dz) {
-        set_err("forward: dropout is not supported in MXFP8 mode or with implicit dz");
-        return false;
-    }
+    if (!admit(net, Mode::Dropout, "forward")) return false;  // (the setters' rule, where the forward would break it)
     const long long step = net->drop_step;
     net->drop_step = (step + 1) & 0xFFFFFFFFll;
     std::vector<KfDropLayer> tab;
@@ -361,9 +353,6 @@ bool drop_prepare(KfNet *net) {
     return true;
 }
 
-#pragma weak kf_specaug_rows
-#pragma weak kf_specaug_apply
-
 // SpecAugment of this forward: which spec-augment layers mask (the switch on and
 // a band or a time mask to draw), their storage, and the row_band of each, one launch per
 // layer; fwd_layer applies it. The step advances at every forward while the switch is on, masks
@@ -383,7 +372,7 @@ bool sa_prepare(KfNet *net) {
             set_err("forward: this build of libkaldi_fp16 has no SpecAugment kernels");
             return false;
         }
-        // (an MXFP8 consumer through the alias is refused when the switches are set, network.cpp;
+        // (an MXFP8 consumer through the alias is refused when the switches are set, modes.cpp;
         // nnet_set_row_subsampling admits no spec-augment layer into the compact row set)
         if (!nl.act && !(nl.act = net->dalloc((size_t)net->max_T * dim * 2))) {
             set_err("forward: alloc activation " + nl.L.name);
@@ -408,18 +397,15 @@ bool sa_prepare(KfNet *net) {
     return true;
 }
 
-#pragma weak kf_bn_train_stats
-#pragma weak kf_bn_train_apply
-
 // Training-mode BatchNorm of this forward: every governed layer normalises by its
-// own batch statistics while the switch is on. The switches refuse the combinations below when
-// they are set (network.cpp); this is the same rule where the forward would break it.
+// own batch statistics while the switch is on. The switches refuse the combinations that do
+// not work when they are set (modes.cpp); this is the same rule where the forward would break it.
 bool bnt_prepare(KfNet *net) {
     for (int li : net->bnt_layers) net->layers[li].bnt_act = false;
     if (!bnt_active(net)) return true;
-    if (net->fp8 || net->implicit_dz || net->rs.Tc > 0 || net->dp || !kf_bn_train_stats || !kf_bn_train_apply) {
-        set_err("forward: training-mode BatchNorm is not supported in MXFP8 mode, with implicit dz, row subsampling or "
-                "a data-parallel communicator");
+    if (!admit(net, Mode::BnTrain, "forward")) return false;
+    if (!kf_bn_train_stats || !kf_bn_train_apply) {
+        set_err("forward: this build of libkaldi_fp16 has no training-mode BatchNorm kernels");
         return false;
     }
     for (int li : net->bnt_layers) net->layers[li].bnt_act = net->layers[li].bnt_r != nullptr;

@@ -1,6 +1,8 @@
 // net_internal.h — the host layer's network state and the helpers its translation units
-// share: network.cpp (topology, allocation, parameters, fp8 set-up, sgd / update, data parallel),
-// forward.cpp and backward.cpp. Nothing here is part of the C-ABI (kf_nnet.h).
+// share: network.cpp (topology, allocation, parameters), mxfp8.cpp, modes.cpp (the switches and
+// which of them combine, data parallel), update.cpp (sgd / update / orthonormal constraint),
+// natgrad.cpp, regularize.cpp (dropout, SpecAugment, training-mode BatchNorm), forward.cpp and
+// backward.cpp. Nothing here is part of the C-ABI (kf_nnet.h).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -16,6 +18,31 @@ using kf::LayerType;
 #define KF_HIDDEN __attribute__((visibility("hidden")))  // internal to libkaldi_fp16_nnet.so
 
 KF_HIDDEN void set_err(const std::string &s);
+
+// The entry points of the newer kernels (update, orthonormal constraint, natural gradient,
+// dropout, SpecAugment, training-mode BatchNorm) are weak references: a program that links the
+// host layer against a backend without them still links, and the nnet_* call that needs one
+// reports it missing.
+#pragma weak kf_update_maxchange
+#pragma weak kf_update_scratch_bytes
+#pragma weak kf_orthonormal_constrain
+#pragma weak kf_orthonormal_scratch_bytes
+#pragma weak kf_ng_init
+#pragma weak kf_ng_default_opts
+#pragma weak kf_ng_apply_scratch_bytes
+#pragma weak kf_ng_state_scratch_bytes
+#pragma weak kf_ng_trx
+#pragma weak kf_ng_scales
+#pragma weak kf_ng_apply
+#pragma weak kf_ng_state
+#pragma weak kf_dropout_masks
+#pragma weak kf_row_seg
+#pragma weak kf_specaug_rows
+#pragma weak kf_specaug_apply
+#pragma weak kf_bn_train_stats
+#pragma weak kf_bn_train_apply
+#pragma weak kf_bn_train_bwd_stats
+#pragma weak kf_bn_train_bwd_apply
 
 struct ParamRef {
     std::string name;
@@ -401,6 +428,20 @@ inline float *gptr(KfNet *net, int pi) { return pi < 0 ? nullptr : net->grad + n
 bool ck(int rc, const char *what);
 // a network from nnet_create_layout has no device storage
 bool on_device(const KfNet *net, const char *what);
+// the layer of that name, or NULL (also for a null net or name)
+NetLayer *find_layer(KfNet *net, const char *name);
+// a list getter's answer: the first n entries to idx (may be NULL), the list's length returned
+inline int list_get(const std::vector<int> &v, int *idx, int n) {
+    for (int i = 0; idx && i < n && i < (int)v.size(); ++i) idx[i] = v[i];
+    return (int)v.size();
+}
+
+// ---- the modes that cannot all be combined (modes.cpp: the table) ----
+enum class Mode { Fp8, ImplicitDz, RowSubsampling, NaturalGradient, DataParallel, Dropout, BnTrain, SpecAugment,
+                  BackwardN /* nnet_backward_n: never "on", only refused */ };
+// may `turning_on` be switched on (or nnet_backward_n run) beside the modes that are on? false
+// with the error text set, "<fn>: not supported <the mode that is on>[: <reason>]"
+bool admit(KfNet *net, Mode turning_on, const char *fn);
 
 inline bool is_trainable(LayerType t) {
     return t == LayerType::ConvReluBN || t == LayerType::TDNNF || t == LayerType::Linear ||
@@ -450,7 +491,11 @@ inline const void *act_of(KfNet *net, int idx) {
     return nl.act_alias && !nl.sa_act ? act_of(net, nl.input) : nl.act;
 }
 
-// ---- MXFP8 forward (network.cpp: set-up and weight quantisation) ----
+// ---- MXFP8 forward (mxfp8.cpp: set-up and weight quantisation) ----
+// the MXFP8 weight copies from the fp16 weights (alloc: the first time)
+bool quantise_weights(KfNet *net, bool alloc);
+// "layer <name> would read the unmasked MXFP8 copy of a spec-augment layer's input", or ""
+std::string sa_mx_conflict(const KfNet *net);
 inline int pad128(int x) { return (x + 127) / 128 * 128; }
 // MXFP8 operand over an Mx tensor of T rows: plain, or spliced [x(t+dt0) | x(t+dt1)]
 inline KfOperand op_mx(const Mx &m, int T, int nparts, int dt0, int dt1) {

@@ -8,12 +8,15 @@
 // events are small integer handles. Single-threaded by construction: the call order is
 // the order of the lines. kf_dp_* comes from the real csrc/dp.cpp (for kf_dp_plan); the
 // few HIP entry points that file references are defined at the bottom and never called,
-// because no communicator is bound.
+// because no communicator is bound. The small int32 tables the host uploads
+// (bridge_transfer_int32) are kept beside their fake address, so a kernel entry that takes
+// only the device copy of a table (kf_update_maxchange) can print it.
 #include <cinttypes>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -32,6 +35,7 @@ std::vector<Alloc> g_allocs;
 uintptr_t g_next = kBase;
 uintptr_t g_stream = 0;       // current stream handle (0 = the default stream)
 int g_nstreams = 0, g_nevents = 0, g_wgrad_target = 512;
+std::map<uintptr_t, std::vector<int32_t>> g_tables;  // what bridge_transfer_int32 uploaded, by address
 
 std::string P(const void *p) {
     if (!p) return "null";
@@ -90,7 +94,11 @@ std::string epi(const KfEpilogue *e) {
              P(e->out2).c_str(), e->ldo2, P(e->scale2).c_str(), P(e->mask_in).c_str(), P(e->out8).c_str(), e->ldo8,
              P(e->scale8).c_str(), e->out8_src, P(e->edge_out).c_str(), e->edge_r0, e->edge_r1, e->edge_src,
              e->row_group, e->row_stride);
-    return b;
+    if (!e->drop && !e->ld_drop && !e->row_seg) return b;
+    // the per-sequence dropout fields, only when one is set
+    std::string s(b, strlen(b) - 1);
+    snprintf(b, sizeof b, " drop=%s ld_drop=%lld row_seg=%s}", P(e->drop).c_str(), e->ld_drop, P(e->row_seg).c_str());
+    return s + b;
 }
 std::string att(const KfAttention *a) {
     char b[256];
@@ -105,6 +113,50 @@ std::string qjob(const KfQuantJob &j) {
              j.ld_src, j.rows, j.cols, j.transpose, P(j.q).c_str(), j.ldq, P(j.scales).c_str(), j.lds);
     return b;
 }
+// a table of n entries, element by element
+template <class T, class F>
+std::string table(const T *t, int n, F one) {
+    if (!t) return "null";
+    std::string s = "[";
+    for (int i = 0; i < n; ++i) s += (i ? " " : "") + one(t[i]);
+    return s + "]";
+}
+// a table the kernel reads from device memory: the copy the host uploaded to that address
+template <class T, class F>
+std::string dev_table(const void *dev, int n, F one) {
+    const auto it = g_tables.find((uintptr_t)dev);
+    if (it == g_tables.end() || it->second.size() * 4 < (size_t)n * sizeof(T)) return P(dev) + "(not uploaded)";
+    std::vector<T> t((size_t)n);
+    memcpy(t.data(), it->second.data(), (size_t)n * sizeof(T));
+    return P(dev) + "=" + table(t.data(), n, one);
+}
+std::string fmt(const char *f, ...) {
+    char b[256];
+    va_list ap;
+    va_start(ap, f);
+    vsnprintf(b, sizeof b, f, ap);
+    va_end(ap);
+    return b;
+}
+std::string seg(const KfUpdSegment &g) { return fmt("{%lld..%lld comp=%d wg=%d}", g.begin, g.end, g.comp, g.first_wg); }
+std::string ucomp(const KfUpdComp &c) {
+    return fmt("{max_change=%g l2=%g lr_factor=%g wg=%d+%d}", c.max_change, c.l2, c.lr_factor, c.first_wg, c.num_wg);
+}
+std::string omat(const KfOrthoMat &m) { return fmt("{off=%lld K=%d n=%d c=%g}", m.offset, m.K, m.n, m.c); }
+std::string ngpre(const KfNgPre &p) {
+    return fmt("{D=%d R=%d w=%lld h=%lld s=%lld st=%lld}", p.D, p.R, p.w_off, p.h_off, p.s_off, p.st_off);
+}
+std::string ngcomp(const KfNgComp &c) {
+    return fmt("{dw=%lld db=%lld K=%d N=%d in=%d out=%d}", c.dw_off, c.db_off, c.K, c.N, c.pre_in, c.pre_out);
+}
+std::string ngopts(const KfNgOpts *o) {
+    if (!o) return "null";
+    return fmt("{rank_in=%d rank_out=%d period=%d history=%g alpha=%g eps=%g delta=%g}", o->rank_in, o->rank_out,
+               o->update_period, o->num_samples_history, o->alpha, o->epsilon, o->delta);
+}
+std::string dlayer(const KfDropLayer &d) {
+    return fmt("{mask=%s ld=%lld dim=%d ord=%d p=%g}", P(d.mask).c_str(), d.ld, d.dim, d.ordinal, d.p);
+}
 
 }  // namespace
 
@@ -116,6 +168,7 @@ extern "C" void stub_reset(void) {
     g_stream = 0;
     g_nstreams = g_nevents = 0;
     g_wgrad_target = 512;
+    g_tables.clear();
 }
 
 extern "C" {
@@ -139,8 +192,9 @@ int bridge_transfer_fp16(void *dst, const uint16_t *, size_t count) {
     line("bridge_transfer_fp16 %s %zu", P(dst).c_str(), count);
     return 0;
 }
-int bridge_transfer_int32(void *dst, const int32_t *, size_t count) {
+int bridge_transfer_int32(void *dst, const int32_t *src, size_t count) {
     line("bridge_transfer_int32 %s %zu", P(dst).c_str(), count);
+    g_tables[(uintptr_t)dst].assign(src, src + count);
     return 0;
 }
 int bridge_transfer_float32(void *dst, const float *, size_t count) {
@@ -357,6 +411,142 @@ int kf_rows_wgrad(const void *x, long long ldx, const void *g, long long ldg, fl
 }
 int kf_scale_cols(const void *x, long long ldx, const float *scale, void *y, long long ldy, int rows, int cols) {
     line("kf_scale_cols %s %lld %s %s %lld %d %d", P(x).c_str(), ldx, P(scale).c_str(), P(y).c_str(), ldy, rows, cols);
+    return 0;
+}
+
+// ---- Kaldi-style update, orthonormal constraint ----
+long long kf_update_scratch_bytes(long long n, int nseg, int ncomp) {
+    const long long b = 256 * (n / KF_UPD_CHUNK + nseg + 2 * (long long)ncomp + 3);
+    line("kf_update_scratch_bytes %lld %d %d -> %lld", n, nseg, ncomp, b);
+    return b;
+}
+int kf_update_maxchange(float *w32, void *w16, const float *g, float *v, long long n, const KfUpdSegment *segments,
+                        int nseg, const KfUpdComp *comps, int ncomp, float lr, float momentum, float max_param_change,
+                        float l2_scale, void *scratch, float *stats) {
+    line("kf_update_maxchange %s %s %s %s %lld segs=%s comps=%s lr=%g mom=%g max_param_change=%g l2_scale=%g "
+         "scratch=%s stats=%s",
+         P(w32).c_str(), P(w16).c_str(), P(g).c_str(), P(v).c_str(), n, dev_table<KfUpdSegment>(segments, nseg, seg).c_str(),
+         dev_table<KfUpdComp>(comps, ncomp, ucomp).c_str(), lr, momentum, max_param_change, l2_scale, P(scratch).c_str(),
+         P(stats).c_str());
+    return 0;
+}
+long long kf_orthonormal_scratch_bytes(const KfOrthoMat *mats, int nmat) {
+    long long b = 256;
+    for (int i = 0; i < nmat; ++i) b += 4ll * mats[i].n * mats[i].n * ((mats[i].K + KF_ORTHO_KCHUNK - 1) / KF_ORTHO_KCHUNK + 1);
+    line("kf_orthonormal_scratch_bytes %s -> %lld", table(mats, nmat, omat).c_str(), b);
+    return b;
+}
+int kf_orthonormal_constrain(float *w32, void *w16, long long n_params, const KfOrthoMat *mats, const KfOrthoMat *mats_dev,
+                             int nmat, void *scratch, float *stats) {
+    line("kf_orthonormal_constrain %s %s %lld mats=%s dev=%s scratch=%s stats=%s", P(w32).c_str(), P(w16).c_str(), n_params,
+         table(mats, nmat, omat).c_str(), P(mats_dev).c_str(), P(scratch).c_str(), P(stats).c_str());
+    return 0;
+}
+
+// ---- natural gradient ----
+void kf_ng_default_opts(KfNgOpts *o) {  // Kaldi's defaults, as csrc/natgrad.hip
+    line("kf_ng_default_opts");
+    if (!o) return;
+    o->rank_in = 20;
+    o->rank_out = 80;
+    o->update_period = 4;
+    o->num_samples_history = 2000.f;
+    o->alpha = 4.f;
+    o->epsilon = 1e-10f;
+    o->delta = 5e-4f;
+}
+int kf_ng_init(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, float *w32, void *w16,
+               double *sc) {
+    line("kf_ng_init pres=%s dev=%s opts=%s %s %s %s", table(pres, npre, ngpre).c_str(), P(pres_dev).c_str(),
+         ngopts(opts).c_str(), P(w32).c_str(), P(w16).c_str(), P(sc).c_str());
+    return 0;
+}
+int kf_ng_trx(const KfOperand *op, int ones, float *out) {
+    line("kf_ng_trx %s ones=%d %s", opnd(op).c_str(), ones, P(out).c_str());
+    return 0;
+}
+int kf_ng_scales(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, const double *sc,
+                 const float *stat, float *report) {
+    line("kf_ng_scales pres=%s dev=%s opts=%s %s %s %s", table(pres, npre, ngpre).c_str(), P(pres_dev).c_str(),
+         ngopts(opts).c_str(), P(sc).c_str(), P(stat).c_str(), P(report).c_str());
+    return 0;
+}
+long long kf_ng_apply_scratch_bytes(const KfNgComp *comps, int ncomp, const KfNgPre *pres, int npre) {
+    long long b = 256;
+    for (int i = 0; i < ncomp; ++i) b += 4ll * KF_NG_MAX_RANK * (comps[i].K + 1 + comps[i].N);
+    line("kf_ng_apply_scratch_bytes comps=%s pres=%s -> %lld", table(comps, ncomp, ngcomp).c_str(),
+         table(pres, npre, ngpre).c_str(), b);
+    return b;
+}
+int kf_ng_apply(float *g, long long n_grad, const KfNgComp *comps, const KfNgComp *comps_dev, int ncomp, const KfNgPre *pres,
+                const KfNgPre *pres_dev, int npre, const float *w32, const float *report, void *scratch) {
+    line("kf_ng_apply %s %lld comps=%s dev=%s pres=%s dev=%s %s %s %s", P(g).c_str(), n_grad,
+         table(comps, ncomp, ngcomp).c_str(), P(comps_dev).c_str(), table(pres, npre, ngpre).c_str(), P(pres_dev).c_str(),
+         P(w32).c_str(), P(report).c_str(), P(scratch).c_str());
+    return 0;
+}
+long long kf_ng_state_scratch_bytes(const KfNgPre *pres, int npre) {
+    const long long b = 256 + 1024ll * npre;
+    line("kf_ng_state_scratch_bytes pres=%s -> %lld", table(pres, npre, ngpre).c_str(), b);
+    return b;
+}
+int kf_ng_state(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, int update, float *w32,
+                void *w16, double *sc, const float *stat, void *scratch, float *report) {
+    line("kf_ng_state pres=%s dev=%s opts=%s update=%d %s %s %s %s %s %s", table(pres, npre, ngpre).c_str(),
+         P(pres_dev).c_str(), ngopts(opts).c_str(), update, P(w32).c_str(), P(w16).c_str(), P(sc).c_str(), P(stat).c_str(),
+         P(scratch).c_str(), P(report).c_str());
+    return 0;
+}
+
+// ---- dropout, SpecAugment, training-mode BatchNorm ----
+int kf_dropout_masks(int n, const KfDropLayer *layers, int B, unsigned long long seed, long long step) {
+    line("kf_dropout_masks %s B=%d seed=%llu step=%lld", table(layers, n, dlayer).c_str(), B, seed, step);
+    return 0;
+}
+int kf_row_seg(int32_t *row_seg, const int *dev_seq_off, int B, int T, int tc0, int tc) {
+    line("kf_row_seg %s %s %d %d %d %d", P(row_seg).c_str(), P(dev_seq_off).c_str(), B, T, tc0, tc);
+    return 0;
+}
+int kf_specaug_rows(int32_t *row_band, const int *dev_seq_off, int B, int T, int dim, int max_bins, float z, int max_zeroed,
+                    int max_kept, unsigned ordinal, unsigned long long seed, long long step) {
+    line("kf_specaug_rows %s %s %d %d dim=%d max_bins=%d z=%g max_zeroed=%d max_kept=%d ord=%u seed=%llu step=%lld",
+         P(row_band).c_str(), P(dev_seq_off).c_str(), B, T, dim, max_bins, z, max_zeroed, max_kept, ordinal, seed, step);
+    return 0;
+}
+int kf_specaug_apply(const void *x, long long ldx, void *y, long long ldy, long long rows, int dim, const int32_t *row_band) {
+    line("kf_specaug_apply %s %lld %s %lld %lld %d %s", P(x).c_str(), ldx, P(y).c_str(), ldy, rows, dim, P(row_band).c_str());
+    return 0;
+}
+int kf_bn_train_stats(const void *r, long long ld, int rows, int D, float eps, float target_rms, float *mean, float *var,
+                      float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq) {
+    line("kf_bn_train_stats %s %lld %d %d eps=%g rms=%g %s %s %s %s acc=%s %s %s", P(r).c_str(), ld, rows, D, eps, target_rms,
+         P(mean).c_str(), P(var).c_str(), P(scale).c_str(), P(shift).c_str(), P(acc_count).c_str(), P(acc_sum).c_str(),
+         P(acc_sumsq).c_str());
+    return 0;
+}
+int kf_bn_train_apply(const void *r, long long ld, int rows, int D, const float *scale, const float *shift, const float *drop,
+                      long long ld_drop, const int32_t *row_seg, const void *resid, long long ldr, float alpha, void *out,
+                      long long ldo) {
+    line("kf_bn_train_apply %s %lld %d %d %s %s drop=%s %lld %s resid=%s %lld alpha=%g out=%s %lld", P(r).c_str(), ld, rows, D,
+         P(scale).c_str(), P(shift).c_str(), P(drop).c_str(), ld_drop, P(row_seg).c_str(), P(resid).c_str(), ldr, alpha,
+         P(out).c_str(), ldo);
+    return 0;
+}
+int kf_bn_train_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int D, const float *scale,
+                          const float *shift, float target_rms, const float *drop, long long ld_drop, const int32_t *row_seg,
+                          float *a, float *b) {
+    line("kf_bn_train_bwd_stats %s %lld %s %lld %d %d %s %s rms=%g drop=%s %lld %s a=%s b=%s", P(g).c_str(), ldg, P(r).c_str(),
+         ldr, rows, D, P(scale).c_str(), P(shift).c_str(), target_rms, P(drop).c_str(), ld_drop, P(row_seg).c_str(),
+         P(a).c_str(), P(b).c_str());
+    return 0;
+}
+int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r, long long ldr, int rows, int D, const float *scale,
+                          const float *shift, float target_rms, const float *a, const float *b, const float *drop,
+                          long long ld_drop, const int32_t *row_seg, const uint8_t *mask, long long ld_mask, void *dz,
+                          long long lddz) {
+    line("kf_bn_train_bwd_apply %s %lld %s %lld %d %d %s %s rms=%g a=%s b=%s drop=%s %lld %s mask=%s %lld dz=%s %lld",
+         P(g).c_str(), ldg, P(r).c_str(), ldr, rows, D, P(scale).c_str(), P(shift).c_str(), target_rms, P(a).c_str(),
+         P(b).c_str(), P(drop).c_str(), ld_drop, P(row_seg).c_str(), P(mask).c_str(), ld_mask, P(dz).c_str(), lddz);
     return 0;
 }
 

@@ -4,7 +4,9 @@ The host layer is pure orchestration: its behaviour is the ordered sequence of C
 makes into libkaldi_fp16 and their arguments. tests/host_trace/stub_backend.cpp defines every
 such symbol as a function that prints one line; tests/host_trace/trace_main.cpp drives nnet_*
 through the scenarios (every config, stream placements, row sets at every residue of
-(T - 1) % 3, fp8, implicit dz, the debug hooks, negative cases). Each scenario's SHA-256 and
+(T - 1) % 3, fp8, implicit dz, the debug hooks, the Kaldi-style update, the orthonormal
+constraint, natural gradient, dropout, SpecAugment, training-mode BatchNorm, every pair of
+modes that cannot be combined, negative cases). Each scenario's SHA-256 and
 line count (and a short digest of every line) are pinned in tests/golden/host_trace.json,
 so a refactor of the host layer that moves, drops or changes one launch, argument, stream, event, allocation or error text fails
 here, without a GPU.
@@ -168,6 +170,15 @@ def test_host_trace_matches_golden(traces):
     if os.environ.get("HOST_TRACE_UPDATE") == "1":
         _write_golden(_digest(_split(text)))
     _check(text, traces[0], "plain")
+
+
+def test_dropout_switched_off_is_the_plain_trace(traces):
+    """With the dropout switch off the host layer makes the calls it makes when the switch was
+    never touched: the two scenarios differ by the set_dropout status line alone."""
+    scen = _split(_text(traces, "plain"))
+    off = [ln for ln in scen["dropout/off"] if not ln.startswith("-- set_dropout ")]
+    assert len(off) == len(scen["dropout/off"]) - 1
+    assert off == scen["dropout/plain"]
 
 
 def test_host_trace_sanitized(traces):
