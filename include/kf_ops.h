@@ -603,6 +603,22 @@ void kf_prof_reset(void);
  * the K-steps alternate between the parts; 0: part order. Only the fp32 accumulation
  * order differs. */
 void kf_gemm_debug_kil(int on);
+/* test hook: 1 (default): the long-K N = 160 / 320 products on a two-part spliced A (parts of
+ * >= 512 columns, |dt| <= 8, no mask / MXFP8 / dropout / out8) whose 128x160 tiles number at
+ * most 256 go to the single-staging kernel (source rows in LDS once per 64-column chunk,
+ * both parts read from that image); 0: to the tiled kernel; 2: to the single-staging kernel at
+ * every row count (measurements). The outputs are bit-identical. */
+void kf_gemm_debug_splice_once(int on);
+/* diagnostics (tests): the single-staging kernel's plan. out[0] = 1, out[1] = 1 when the kernel
+ * applies (kf_splice_once_debug_last: was launched), else 0 and the rest zero; out[2..] = BM, BN,
+ * the parts' row span max(dt) - min(dt), edge-row slots, zero slots, image rows (= BM + span +
+ * edge slots + zero slots), 1 KiB pieces per image, images in the ring, B ring stages, dynamic
+ * LDS bytes, row tiles, column tiles, B k-contiguous. Writes min(n, 16) ints, returns that count.
+ * _plan: for the given product, without a launch or any HIP call (-1: an invalid operand);
+ * _last: of the calling thread's last kf_gemm_fused that reached this dispatch. */
+int kf_splice_once_debug_plan(int M, int N, int K, const KfOperand *A, const KfOperand *B,
+                              const KfEpilogue *epi, int *out, int n);
+int kf_splice_once_debug_last(int *out, int n);
 /* n <= KF_TRANSPOSE_MAX fp16 transposes in one launch: dst[j] [N[j] x M[j]] = src[j]^T
  * (src[j] [M[j] x N[j]] row-major); the network's transposed weight copies */
 #define KF_TRANSPOSE_MAX 48

@@ -31,9 +31,7 @@
 //     (t - tbase) * hpos + h + ctap[p]
 // with ctap[p] = (dt_p - dtmin) * hpos + ((dh_p + pad) % hmul) * hpe + (dh_p + pad) / hmul.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int halo_off(int R, int c) {
-    return (R >> 3) * 1024 + 256 * (c >> 1) + 16 * ((c + 2 * R) & 15);
-}
+// (halo_off: gemm_common.h, shared with splice_once.hip)
 struct HaloArgs {
     const h16 *x;           // source [T x ...] rows of ld elements, heights of pw channels
     long long ld;

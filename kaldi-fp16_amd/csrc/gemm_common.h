@@ -86,6 +86,13 @@ __device__ __forceinline__ long long op_off(const OpD &d, int t, int h, int kk, 
 constexpr int BK = 64;
 // k-contiguous [rows][64] halves: 16-byte chunk c of row r at slot c ^ ((r>>1)&7)
 __device__ __forceinline__ int kc_off(int r, int c) { return r * 128 + 16 * (c ^ ((r >> 1) & 7)); }
+// k-contiguous source-row images read at a per-lane row offset (the conv halo kernels'
+// images, conv_halo.hip's header comment, and splice_once.hip's): 16-byte chunk c of row R in
+// 1 KiB piece R / 8, slot (c + 2R) mod 16 of 256-byte block c / 2. A fragment read hits 16
+// distinct slots whenever its 16 rows are consecutive, whatever the first row
+__device__ __forceinline__ int halo_off(int R, int c) {
+    return (R >> 3) * 1024 + 256 * (c >> 1) + 16 * ((c + 2 * R) & 15);
+}
 // reduction-major [64][W] halves: 8-byte unit u of row r at u ^ swz(r). One
 // ds_read_b64_tr_b16 reads rows {8g + q (+4)} x 4 units in each 32-lane group; the
 // swizzle spreads those 8 rows over all 64 banks for the row stride's residue:

@@ -1,5 +1,5 @@
 // gemm_fused.hip — kf_gemm_fused / kf_gemm_fused_edge (kf_ops.h): validation, the choice of
-// kernel (MXFP8, masked A, conv halo, tile) and the gemm_kernel instantiations with a
+// kernel (MXFP8, masked A, conv halo, single-staged splice, tile) and the gemm_kernel instantiations with a
 // k-contiguous B. The reduction-major-B ones are gemm_fused_mn.hip's.
 #include "gemm_fused.h"
 
@@ -147,6 +147,12 @@ static int fused_impl(int M, int N, int K, const KfOperand *A, const KfOperand *
         kf_report_error("kf_gemm_fused: time-strided rows (tmul / t0) and grouped output rows (row_group) need a "
                         "conv on the halo kernel (M=%d N=%d K=%d)", M, N, K);
         return -1;
+    }
+    // long-K N = 160 / 320 products on a two-part spliced A at the 128x160 tiles' row counts: the
+    // source rows staged once per 64-column chunk (splice_once.hip; it declines everything else)
+    if (!f8) {
+        const int sr = splice_once_try(M, N, K, a, b, B->kcontig != 0, E);
+        if (sr != 0) return sr < 0 ? -1 : 0;
     }
     // Tiles: 384x160 8-wave for N = 160 / 320; 256x64 for N <= 64; for
     // N >= 256 192x128 (or 128x192, below) 8-wave tiles (80 KB of LDS: two workgroups share a CU and one's

@@ -39,6 +39,10 @@ double epi_bytes(const KfEpilogue &E, long long M, long long N);
 unsigned long long *kf_gemm_trace_take(int *blk);
 // conv_halo_kernel (conv_halo.hip) for a fused product on a conv im2col / col2im operand
 int conv_halo_try(int M, int N, int K, const OpD &a, const OpD &b, int bm, bool bkc, const KfEpilogue &E);
+// splice_once_kernel (splice_once.hip) for a long-K N = 160 / 320 product on a two-part spliced A
+// whose 128x160 tiles fit one round of workgroups: 1 launched, 0 not applicable (the caller runs the tiled
+// kernel), -1 error
+int splice_once_try(int M, int N, int K, const OpD &a, const OpD &b, bool bkc, const KfEpilogue &E);
 #pragma GCC visibility pop
 
 static inline int op_mode(const OpD &o) {

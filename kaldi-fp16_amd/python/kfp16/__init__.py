@@ -344,6 +344,31 @@ def halo_debug_last() -> dict:
     return d
 
 
+_SPLICE_FIELDS = ("BM", "BN", "span", "edge_slots", "zero_slots", "image_rows", "npieces", "nimg", "b_stages",
+                  "lds", "mtiles", "ntiles", "bkc")
+
+
+def _splice_record(v) -> dict:
+    d = dict(taken=v[1])
+    d.update({k: v[2 + i] for i, k in enumerate(_SPLICE_FIELDS)})
+    return d
+
+
+def splice_once_plan(M, N, K, A, B, E) -> dict:
+    """kf_splice_once_debug_plan: the single-staging kernel's plan for a product (no launch)"""
+    v = (_i * 16)()
+    if core.kf_splice_once_debug_plan(M, N, K, C.byref(A), C.byref(B), C.byref(E), v, 16) < 0:
+        raise KfError("kf_splice_once_debug_plan: " + _err(core.kf_last_error))
+    return _splice_record(v)
+
+
+def splice_once_last() -> dict:
+    """kf_splice_once_debug_last: what the calling thread's last kf_gemm_fused dispatch chose"""
+    v = (_i * 16)()
+    core.kf_splice_once_debug_last(v, 16)
+    return _splice_record(v)
+
+
 def set_stream(stream_handle) -> None:
     core.kf_set_stream(C.c_void_p(stream_handle) if stream_handle else None)
 
@@ -880,6 +905,10 @@ _sig(core, "kf_gemm_wgrad_scaled", _i, _i, _i, _i, C.POINTER(KfOperand), C.POINT
 _sig(core, "kf_gemm_wgrad_target", _i, _i)
 _sig(core, "kf_gemm_debug_kil", None, _i)
 _sig(core, "kf_gemm_trace", None, _vp, _i, _i)
+_sig(core, "kf_gemm_debug_splice_once", None, _i)
+_sig(core, "kf_splice_once_debug_plan", _i, _i, _i, _i, C.POINTER(KfOperand), C.POINTER(KfOperand),
+     C.POINTER(KfEpilogue), C.POINTER(_i), _i)
+_sig(core, "kf_splice_once_debug_last", _i, C.POINTER(_i), _i)
 _sig(core, "kf_halo_debug_last", _i, C.POINTER(_i), _i)
 _sig(core, "kf_quant_mxfp8", _i, _vp, _ll, _i, _i, _i, _vp, _ll, _vp, _ll)
 # non-MFMA layer pieces (csrc/layers.hip) and the ivector input path (csrc/ivector.hip)
