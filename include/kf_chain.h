@@ -36,8 +36,8 @@ typedef struct KfDenGraph KfDenGraph;
 typedef struct KfNumBatch KfNumBatch;
 typedef struct KfChain KfChain;
 
-/* Mirrors ChainTrainingOpts, backward.go:114-140 (xent_regularize is accepted and
- * unused: the xent branch is out of scope). */
+/* Mirrors ChainTrainingOpts, backward.go:114-140. kf_chain_compute does not read
+ * xent_regularize; kf_chain_xent scales the xent output's gradient by it. */
 typedef struct {
     float l2_regularize;
     float out_of_range_regularize;
@@ -114,6 +114,26 @@ const float *kf_chain_seq_stats(const KfChain *c);
 /* Synchronises the stream and sums the per-sequence statistics of the last compute.
  * Fails (-1) when a den exchange timed out in any compute since the previous call. */
 int kf_chain_result(KfChain *c, KfChainResult *out);
+
+/* Kaldi's --chain.xent-regularize: the loss gradient at the affine output of
+ * the log-softmax xent output, and the xent objective, from the numerator posteriors the
+ * compute left on the device. After kf_chain_compute(c, num, opts, ...) on the same stream,
+ * with the same num and opts: rows, frames, stride and nseq are those of that compute.
+ * xent_output: the fp16 log-softmax rows y, leading dimension ldx; xent_grad: fp16, leading
+ * dimension ldg (both >= P, matrices of that compute's num_rows rows). For a supervised row,
+ * with post the posteriors of the in-range pdfs as a dense row and S their computed sum,
+ *   xent_grad[p] = rne_fp16(-xent_regularize * w * (post[p] - exp(y[p]) * S))
+ * (zeros for a sequence whose objective was not finite, and with xent_regularize == 0), and per
+ * sequence objf = w * sum_t sum_p post[p] * y[p] (0 when not finite). Every supervised row's
+ * first P columns are written exactly once; nothing else is touched. A call replays bit for
+ * bit. 0 / -1: no compute before it, another batch than that compute's, ldx or ldg below P,
+ * a NULL pointer. */
+int kf_chain_xent(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
+                  const void *xent_output, long long ldx, void *xent_grad, long long ldg);
+/* Synchronises the stream; the sequences' objectives and weights (w * frames, as the chain
+ * statistics count them) of the last kf_chain_xent, summed in double. Either out pointer
+ * may be NULL. -1 when no kf_chain_xent ran since the last kf_chain_compute. */
+int kf_chain_xent_result(KfChain *c, double *xent_objf, double *total_weight);
 
 /* diagnostics: phase timestamps of the den forward kernel (sequence 0, block 0,
  * frames 16..47, 8 u64 each, 100 MHz wall clock), then the arc-phase end of every wave

@@ -82,6 +82,20 @@ int nnet_forward(KfNet *net, const void *features_dev, int T);
 const void *nnet_activation(const KfNet *net, const char *layer, int *rows, int *cols);
 /* backward from the fp16 gradient of the chain output [T x num_pdfs] */
 int nnet_backward(KfNet *net, const void *out_grad_dev);
+/* Backward with two seeds (Kaldi's chain xent-regularize): out_grad_dev as
+ * nnet_backward takes it, and xent_grad_dev, the fp16 loss gradient [rows x P_xent] (leading
+ * dimension P_xent) at the affine output of the log-softmax output layer named output-xent, as
+ * kf_chain_xent writes it; both in the forward's row form (full rows, or the compact rows
+ * under row subsampling). The xent branch (output-xent down to the branch point, a
+ * linear-component on the chain output's path: prefinal-l) gets its weight gradients, and every
+ * layer from the branch point down the gradient of both outputs: the branch's gradient at the
+ * branch point is rounded to fp16 once (gx) and added in the input-gradient epilogue of the
+ * chain-path layer above the branch point, g = rne(acc + gx). An error on a net without
+ * output-xent, when the path from it does not reach the chain output's path, when the branch
+ * point is not a linear-component, in MXFP8 mode and on a net bound to data parallel. With
+ * natural gradient on, the branch's components keep plain gradients. nnet_backward is
+ * unchanged: it zeroes the branch's gradients. */
+int nnet_backward_xent(KfNet *net, const void *out_grad_dev, const void *xent_grad_dev);
 float *nnet_grad_buffer(KfNet *net);   /* device fp32 [num_params] */
 /* use caller-owned device memory (>= num_params fp32) as the gradient buffer */
 int nnet_bind_grad_buffer(KfNet *net, float *dev);

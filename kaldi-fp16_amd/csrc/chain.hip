@@ -8,9 +8,11 @@
 //   chain_tables.cpp  host-side table builders and graph validation, no HIP
 //   chain_num.hip     numerator: k_num_fb + k_num_post (FST in LDS), k_logfb (any FST, ABI)
 //   chain_den.hip     denominator: k_den_fwd, k_den_fb, k_den_post, the exchange
+//   chain_xent.hip    the xent output's derivative and objective: k_chain_xent (kf_chain_xent)
 //   chain_abi.hip     the reference ABIs chain.h, chain_backward_api.h, chain_den.h
 #include "chain_denom.h"
 #include "chain_num.h"
+#include "chain_xent.h"
 #include "kf_prof.h"
 #include "../../include/kf_ops.h"
 
@@ -82,6 +84,11 @@ struct KfChain {
     float *alpha_store = nullptr, *beta_store = nullptr, *asum_store = nullptr, *bsum_store = nullptr;
     float *stats = nullptr;
     float *h_stats = nullptr;     // pinned [max_seqs][8] (kf_chain_result)
+    // kf_chain_xent (made at its first call): the per-frame objective terms [max_seqs][max_frames],
+    // their pinned copy with the statistics behind it (kf_chain_xent_result), and whether
+    // one ran since the last compute
+    float *xent_part = nullptr, *h_xent = nullptr;
+    bool xent_ran = false;
     float *num_ab = nullptr;      // numerator alpha/beta
     size_t num_ab_cap = 0;
     float *num_post = nullptr;    // sparse numerator posteriors
@@ -112,6 +119,8 @@ struct KfChain {
             if (h_stage[i]) hipHostFree(h_stage[i]);
         }
         if (h_stats) hipHostFree(h_stats);
+        if (h_xent) hipHostFree(h_xent);
+        if (xent_part) hipFree(xent_part);
         if (side) hipStreamDestroy(side);
         if (ev_in) hipEventDestroy(ev_in);
         if (ev_num) hipEventDestroy(ev_num);
@@ -538,6 +547,7 @@ extern "C" int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChain
     if (!compute_args_ok(c, num, opts, nnet_output, ld, nseq, seq_row0, seq_frames, stride, out_grad, ldg))
         return -1;
     hipStream_t st = kf_stream();
+    c->xent_ran = false;
     // a refilled numerator batch (kf_num_batch_refill): its copy lands before anything reads it
     if (num->ev_copy) hipStreamWaitEvent(st, num->ev_copy, 0);
     if (!c->last.matches(num->gen, nseq, stride, nnet_output, ld, num_rows, seq_row0, seq_frames) &&
@@ -549,6 +559,105 @@ extern "C" int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChain
         kfc_set_error("kf_chain_compute: launch failed");
         return -1;
     }
+    return 0;
+}
+
+// The xent output's derivative and objective (chain_xent.hip) over the layout and the numerator
+// posteriors of the compute before it, on the same stream: the posteriors, the descriptors and
+// the statistics' ok are ahead of it there (kf_chain_compute joined the numerator stream).
+extern "C" int kf_chain_xent(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts, const void *xent_output,
+                             long long ldx, void *xent_grad, long long ldg) {
+    kf_take_pending(__func__);
+    if (!c || !num || !opts || !xent_output || !xent_grad) {
+        kfc_set_error("kf_chain_xent: NULL argument");
+        return -1;
+    }
+    if (c->last.gen == 0) {
+        kfc_set_error("kf_chain_xent: no kf_chain_compute before it");
+        return -1;
+    }
+    if (num->gen != c->last.gen || (int)num->nd->desc.size() != c->last.nseq) {
+        kfc_set_error("kf_chain_xent: the numerator batch is not the one of the last kf_chain_compute");
+        return -1;
+    }
+    const int P = c->den->t->dev.P, nseq = c->last.nseq;
+    if (ldx < P || ldg < P) {
+        kfc_set_error("kf_chain_xent: ldx %lld / ldg %lld below P %d", ldx, ldg, P);
+        return -1;
+    }
+    if (!c->xent_part) {
+        const size_t n = (size_t)c->max_seqs * c->max_frames;
+        if (hipMalloc(&c->xent_part, n * 4) != hipSuccess ||
+            hipHostMalloc((void **)&c->h_xent, (n + (size_t)c->max_seqs * 8) * 4, hipHostMallocDefault) != hipSuccess) {
+            if (c->xent_part) hipFree(c->xent_part);
+            c->xent_part = nullptr;
+            c->h_xent = nullptr;
+            kf_take_pending("kf_chain_xent allocation");
+            kfc_set_error("kf_chain_xent: allocation failed");
+            return -1;
+        }
+    }
+    XentRun r{};
+    r.nums = c->d_desc;
+    r.row0 = c->d_row0;
+    r.frames = c->d_frames;
+    r.stats = c->stats;
+    r.y = (const h16 *)xent_output;
+    r.ldx = ldx;
+    r.grad = (h16 *)xent_grad;
+    r.ldg = ldg;
+    r.part = c->xent_part;
+    r.part_ld = c->max_frames;
+    r.P = P;
+    r.stride = c->last.stride;
+    r.w = opts->supervision_weight;
+    r.scale = opts->xent_regularize * opts->supervision_weight;
+    double frames = 0;
+    for (int f : c->last.frames) {
+        frames += f;
+        r.max_t = std::max(r.max_t, f);
+    }
+    launch_chain_xent(r, nseq, frames);
+    if (hipGetLastError() != hipSuccess) {
+        kfc_set_error("kf_chain_xent: launch failed");
+        return -1;
+    }
+    c->xent_ran = true;
+    return 0;
+}
+
+// Synchronises; the per-frame terms of every sequence summed in double, frame by frame and
+// sequence by sequence (a fixed order), and the weights the chain statistics count.
+extern "C" int kf_chain_xent_result(KfChain *c, double *xent_objf, double *total_weight) {
+    if (!c) {
+        kfc_set_error("kf_chain_xent_result: NULL argument");
+        return -1;
+    }
+    kf_take_pending(__func__);
+    if (!c->xent_ran) {
+        kfc_set_error("kf_chain_xent_result: no kf_chain_xent since the last kf_chain_compute");
+        return -1;
+    }
+    const int n = c->last.nseq;
+    const size_t np = (size_t)c->max_seqs * c->max_frames;
+    hipStream_t st = kf_stream();
+    // (one copy of the first n sequences' rows; only the frames the kernel wrote are read below)
+    bool ok = hipMemcpyAsync(c->h_xent, c->xent_part, (size_t)n * c->max_frames * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(c->h_xent + np, c->stats, (size_t)n * 8 * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (!ok || hipStreamSynchronize(st) != hipSuccess) {
+        kf_take_pending("kf_chain_xent_result copy");
+        kfc_set_error("kf_chain_xent_result: copy failed");
+        return -1;
+    }
+    double objf = 0.0, wsum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        double o = 0.0;
+        for (int t = 0; t < c->last.frames[i]; ++t) o += c->h_xent[(size_t)i * c->max_frames + t];
+        objf += o;
+        wsum += c->h_xent[np + (size_t)i * 8 + 4];
+    }
+    if (xent_objf) *xent_objf = objf;
+    if (total_weight) *total_weight = wsum;
     return 0;
 }
 

@@ -17,6 +17,7 @@ enum {
     KF_PROF_HALO = 4,        // conv halo forward / input gradient
     KF_PROF_HALO_WGRAD = 5,  // conv halo weight gradient
     KF_PROF_REDUCE = 6,      // split-K slab reduce
+    KF_PROF_CHAIN_XENT = 7,  // chain xent derivative (kf_chain_xent)
 };
 
 // bracket of any launch sequence on the current stream (two event records): returns a

@@ -227,6 +227,12 @@ struct BackwardPass {
     size_t dp_next = 0;
     const void *dz;    // gradient w.r.t. pre-activation of the current layer
     const void *gcur;  // stored gradient w.r.t. the current layer's output
+    // nnet_backward_xent: the xent branch's layers from its output down (NULL: a
+    // chain-only backward), the branch point's width, and the chain-path layer that reads the
+    // branch point. The branch's last step writes its input gradient to net->gx instead of the
+    // dz ring; the join layer's input-gradient epilogue adds it through the residual slot.
+    const std::vector<int> *branch = nullptr;
+    int branch_dim = 0, join_li = -1;
 
     // (the top layer must be the chain output)
     BackwardPass(KfNet *n, const void *out_grad)
@@ -284,6 +290,7 @@ struct BackwardPass {
     bool ng_finish();
 
     bool begin();
+    bool branch_pass(const void *xent_grad, const void *out_grad);
     int step(int li, int ndone);  // 1: go on below, 0: nothing trainable below, -1: failed
     bool finish();
 
@@ -379,7 +386,18 @@ bool BackwardPass::begin() {
         kf_set_stream(mainst);
     }
     if (!to_side()) return false;
-    for (const auto &r : net->offpath) bridge_gpu_memset(net->grad + r.first, 0, (size_t)r.second * 4);
+    // (the xent branch's weight gradients overwrite their ranges: nnet_backward_xent zeroes the rest)
+    auto branch_writes = [&](long long off) {
+        if (!branch) return false;
+        for (int li : *branch) {
+            const NetLayer &q = net->layers[li];
+            for (int pi : {q.pW, q.pb, q.pW2, q.pb2})
+                if (pi >= 0 && net->params[pi].off == off) return true;
+        }
+        return false;
+    };
+    for (const auto &r : net->offpath)
+        if (!branch_writes(r.first)) bridge_gpu_memset(net->grad + r.first, 0, (size_t)r.second * 4);
     // negative control of the data-parallel tests: exchanging before any producer ran
     if (net->dp && net->dp_early) {
         if (!dp_issue(net, dp_next, INT_MAX)) return false;
@@ -413,6 +431,25 @@ bool BackwardPass::begin() {
     return true;
 }
 
+// The xent branch before the chain walk: ordinary steps seeded with the xent output's gradient,
+// on the same rings, events and streams (stepi, flip and nbott advance as for any step, so the
+// ring's hazard argument covers them: they are simply the pass's first steps). The last of them
+// hands its input gradient to net->gx, gx = rne(acc), which the chain walk's join layer adds:
+// g = rne(acc + gx). Both GEMMs run on the chain stream, in order, so the reader is behind the
+// writer without an event; the weight-gradient stream never touches gx; and the next
+// nnet_backward_xent's writer is behind this call's reader, because finish() joins the chain
+// stream into the caller's stream and begin() starts the next pass behind that stream.
+bool BackwardPass::branch_pass(const void *xent_grad, const void *out_grad) {
+    dz = gcur = xent_grad;
+    for (int li : *branch) {
+        const int r = step(li, 0);
+        if (r == 0) set_err("backward_xent: nothing trainable below " + net->layers[li].L.name);
+        if (r != 1) return false;
+    }
+    dz = gcur = out_grad;
+    return true;
+}
+
 int BackwardPass::step(int li, int ndone) {
     done = ndone;
     NetLayer &nl = net->layers[li];
@@ -423,7 +460,8 @@ int BackwardPass::step(int li, int ndone) {
     Step s{nl, li, rows_of(net, li), net->T,
            // (the first compact layer read its input gathered to the compact rows)
            first_c && !net->conv_c ? net->xc : act_of(net, nl.input), nl.needs_dx && nl.input >= 0, first_c,
-           net->dz[flip], net->g[flip],
+           // (the xent branch's last step: its input gradient goes to gx, not into the ring)
+           branch && li == branch->back() ? net->gx : net->dz[flip], net->g[flip],
            // (this step's dbott buffer was last written at step i - 3 or earlier)
            !two ? net->dbott : nbott % 3 == 0 ? net->dbott : nbott % 3 == 1 ? net->dbott2 : net->dbott3, KfEpilogue()};
     if (!side_wait(stepi - 3)) return -1;
@@ -434,6 +472,17 @@ int BackwardPass::step(int li, int ndone) {
         s.E.resid = gcur;
         s.E.ldr = L.out_dim;
         s.E.resid_alpha = (float)L.bypass_scale;
+    }
+    if (branch && li == join_li) {
+        // the branch point is a linear-component: it has no bypass, so its producer's residual
+        // slot is free
+        if (!s.want_dx || s.E.resid || s.E.out || !s.E.out2) {
+            set_err("backward_xent: the input gradient of " + L.name + " cannot take the xent branch's gradient");
+            return -1;
+        }
+        s.E.resid = net->gx;
+        s.E.ldr = branch_dim;
+        s.E.resid_alpha = 1.f;
     }
     bool ok = true;
     switch (L.type) {
@@ -1057,14 +1106,23 @@ bool BackwardPass::conv_dgrad_plain(Step &s) {
     return ck(kf_gemm_fused(s.T * L.hin, L.fin, noff * L.fout, &A2, &B2, &E), "conv dgrad");
 }
 
-int backward_impl(KfNet *net, const void *out_grad, int max_layers) {
+// xent_grad != NULL: `branch` holds the xent branch's layers, `join` the chain-path layer that
+// reads the branch point (nnet_backward_xent)
+int backward_impl(KfNet *net, const void *out_grad, int max_layers, const void *xent_grad = nullptr,
+                  const std::vector<int> *branch = nullptr, int join = -1) {
     if (!on_device(net, "backward")) return -1;
     if (net->T <= 0) {
         set_err("backward before forward");
         return -1;
     }
     BackwardPass pass(net, out_grad);
+    if (xent_grad) {
+        pass.branch = branch;
+        pass.join_li = join;
+        pass.branch_dim = net->layers[net->layers[join].input].L.out_dim;
+    }
     if (!pass.begin()) return -1;
+    if (xent_grad && !pass.branch_pass(xent_grad, out_grad)) return -1;
     for (int li = net->chain_out, done = 0; li >= 0 && done < max_layers; li = net->layers[li].input, ++done) {
         const int r = pass.step(li, done);
         if (r < 0) return -1;
@@ -1078,6 +1136,52 @@ int backward_impl(KfNet *net, const void *out_grad, int max_layers) {
 extern "C" int nnet_backward(KfNet *net, const void *out_grad) {
     kf_take_pending(__func__);
     return backward_impl(net, out_grad, 1 << 30);
+}
+// Two seeds: the chain output's gradient and, at the log-softmax output named
+// output-xent, the xent gradient of kf_chain_xent, both in the forward's row form.
+extern "C" int nnet_backward_xent(KfNet *net, const void *out_grad, const void *xent_grad) {
+    kf_take_pending(__func__);
+    if (!on_device(net, "backward_xent")) return -1;
+    if (!out_grad || !xent_grad) {
+        set_err("backward_xent: null gradient");
+        return -1;
+    }
+    int xo = -1;
+    for (size_t i = 0; i < net->layers.size(); ++i)
+        if (net->layers[i].L.type == LayerType::Output && net->layers[i].L.name == "output-xent") xo = (int)i;
+    if (xo < 0 || xo == net->chain_out) {
+        set_err("backward_xent: the network has no output-xent layer beside the chain output");
+        return -1;
+    }
+    std::vector<char> on(net->layers.size(), 0);
+    for (int cur = net->chain_out; cur >= 0; cur = net->layers[cur].input) on[cur] = 1;
+    std::vector<int> branch;
+    int bp = xo;
+    for (; bp >= 0 && !on[bp]; bp = net->layers[bp].input) branch.push_back(bp);
+    if (bp < 0) {
+        set_err("backward_xent: the path from output-xent down does not reach the chain output's path");
+        return -1;
+    }
+    if (net->layers[bp].L.type != LayerType::Linear) {
+        set_err("backward_xent: the branch point " + net->layers[bp].L.name + " is not a linear-component");
+        return -1;
+    }
+    int join = -1;
+    for (int cur = net->chain_out; cur >= 0; cur = net->layers[cur].input)
+        if (net->layers[cur].input == bp) join = cur;
+    if (join < 0 || net->layers[join].bypass) {
+        set_err("backward_xent: no chain-path layer without a bypass reads the branch point " + net->layers[bp].L.name);
+        return -1;
+    }
+    if (!admit(net, Mode::XentBackward, "backward_xent")) return -1;
+    if (!net->gx) {  // the branch's gradient at the branch point, fp16 [max_T x dim]: made once
+        net->gx = net->dalloc((size_t)net->max_T * net->layers[bp].L.out_dim * 2);
+        if (!net->gx) {
+            set_err("backward_xent: alloc the branch gradient");
+            return -1;
+        }
+    }
+    return backward_impl(net, out_grad, 1 << 30, xent_grad, &branch, join);
 }
 // debugging / tests: back-propagate through the top `n` layers only
 extern "C" int nnet_backward_n(KfNet *net, const void *out_grad, int n) {

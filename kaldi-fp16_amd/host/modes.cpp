@@ -6,8 +6,8 @@
 #include "net_internal.h"
 
 // ---------------------------------------------------------------------------
-// The modes that cannot all be combined, each pair stated once. A setter (and nnet_backward_n)
-// asks admit() before it switches its mode on; turning a mode off is never refused. A new
+// The modes that cannot all be combined, each pair stated once. A setter (and nnet_backward_n,
+// nnet_backward_xent) asks admit() before it switches its mode on; turning a mode off is never refused. A new
 // mode is registered here: a value of Mode (net_internal.h), its test in mode_on, its phrase
 // and its rows of the table.
 // ---------------------------------------------------------------------------
@@ -25,7 +25,8 @@ bool mode_on(const KfNet *net, Mode m) {
         case Mode::Dropout: return drop_active(net);
         case Mode::BnTrain: return bnt_active(net);
         case Mode::SpecAugment: return sa_active(net);
-        case Mode::BackwardN: break;
+        case Mode::BackwardN:
+        case Mode::XentBackward: break;
     }
     return false;
 }
@@ -41,7 +42,8 @@ const char *phrase(Mode m) {
         case Mode::Dropout: return "with dropout on (nnet_set_dropout)";
         case Mode::BnTrain: return "with training-mode BatchNorm on (nnet_set_bn_train)";
         case Mode::SpecAugment: return "with SpecAugment on (nnet_set_spec_augment)";
-        case Mode::BackwardN: break;
+        case Mode::BackwardN:
+        case Mode::XentBackward: break;
     }
     return "";
 }
@@ -66,6 +68,9 @@ const Conflict kConflicts[] = {
     {Mode::BackwardN, Mode::NaturalGradient, nullptr, nullptr},
     {Mode::BackwardN, Mode::Dropout, nullptr, nullptr},
     {Mode::BackwardN, Mode::BnTrain, nullptr, nullptr},
+    // (the branch's GEMMs have no MXFP8 form; the bucket plan, backward_groups, walks the chain path)
+    {Mode::XentBackward, Mode::Fp8, nullptr, nullptr},
+    {Mode::XentBackward, Mode::DataParallel, "the gradient buckets are planned for the chain output's path only", nullptr},
 };
 
 }  // namespace

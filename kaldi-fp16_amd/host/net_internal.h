@@ -233,6 +233,9 @@ struct KfNet {
     bool dz_imp[3] = {false, false, false};  // dz[i] was left implicit by the producing epilogue
     bool dz_edge[3] = {false, false, false}; // row T of dz[i] already holds the strided TDNN-F edge sum
     void *w2s = nullptr;              // [kaff x dout] fp16: W2 with the BN scale folded in
+    // nnet_backward_xent: the xent branch's gradient at the branch point, fp16 [max_T x dim],
+    // made at the first call (backward.cpp branch_pass)
+    void *gx = nullptr;
     void *dbott_last = nullptr;  // the dbott buffer of the last TDNN-F / prefinal step (tests)
     void *dz_last = nullptr;     // the input gradient the last backward step handed down (tests)
     size_t edge_half = 0;
@@ -438,8 +441,9 @@ inline int list_get(const std::vector<int> &v, int *idx, int n) {
 
 // ---- the modes that cannot all be combined (modes.cpp: the table) ----
 enum class Mode { Fp8, ImplicitDz, RowSubsampling, NaturalGradient, DataParallel, Dropout, BnTrain, SpecAugment,
-                  BackwardN /* nnet_backward_n: never "on", only refused */ };
-// may `turning_on` be switched on (or nnet_backward_n run) beside the modes that are on? false
+                  BackwardN /* nnet_backward_n: never "on", only refused */,
+                  XentBackward /* nnet_backward_xent: never "on", only refused */ };
+// may `turning_on` be switched on (or nnet_backward_n / nnet_backward_xent run) beside the modes that are on? false
 // with the error text set, "<fn>: not supported <the mode that is on>[: <reason>]"
 bool admit(KfNet *net, Mode turning_on, const char *fn);
 

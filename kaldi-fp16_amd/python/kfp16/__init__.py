@@ -136,6 +136,7 @@ _sig(nnet, "nnet_forward", _i, _vp, _vp, _i)
 _sig(nnet, "nnet_forward_ivector", _i, _vp, _vp, _i, _vp, _i, _vp)
 _sig(nnet, "nnet_activation", _vp, _vp, C.c_char_p, C.POINTER(_i), C.POINTER(_i))
 _sig(nnet, "nnet_backward", _i, _vp, _vp)
+_sig(nnet, "nnet_backward_xent", _i, _vp, _vp, _vp)
 _sig(nnet, "nnet_grad_buffer", _vp, _vp)
 _sig(nnet, "nnet_master_buffer", _vp, _vp)
 _sig(nnet, "nnet_weight_buffer", _vp, _vp)
@@ -465,8 +466,13 @@ class Network:
         p, r, c = self.activation(layer)
         return read_fp16(p, (r, c))
 
-    def backward(self, out_grad_ptr):
-        check(nnet.nnet_backward(self.h, out_grad_ptr), "nnet_backward")
+    def backward(self, out_grad_ptr, xent_grad_ptr=None):
+        """nnet_backward; with xent_grad_ptr (the gradient Chain.xent wrote for the output-xent
+        layer, in the forward's row form) nnet_backward_xent: both outputs' gradients."""
+        if xent_grad_ptr is None:
+            check(nnet.nnet_backward(self.h, out_grad_ptr), "nnet_backward")
+        else:
+            check(nnet.nnet_backward_xent(self.h, out_grad_ptr, xent_grad_ptr), "nnet_backward_xent")
 
     @property
     def grad_ptr(self):

@@ -4,6 +4,7 @@ chain_backward_api.h). Device work only; the CPU restatement lives in oracle/.""
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -48,6 +49,8 @@ class DenFstGPU(C.Structure):
 
 
 def _sig(name, res, *args):
+    if os.environ.get("KFP16_LIBDIR") and not hasattr(core, name):
+        return  # A/B against an older build that lacks this entry point (as kfp16._sig)
     fn = getattr(core, name)
     fn.restype = res
     fn.argtypes = list(args)
@@ -66,6 +69,8 @@ _sig("kf_chain_free", None, _vp)
 _sig("kf_chain_compute", _i, _vp, _vp, C.POINTER(KfChainOpts), _vp, _ll, _ll, _i, _vp, _vp, _i, _vp, _ll)
 _sig("kf_chain_seq_stats", _vp, _vp)
 _sig("kf_chain_result", _i, _vp, C.POINTER(KfChainResult))
+_sig("kf_chain_xent", _i, _vp, _vp, C.POINTER(KfChainOpts), _vp, _ll, _vp, _ll)
+_sig("kf_chain_xent_result", _i, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("kf_chain_debug_spin_limit", None, _vp, C.c_uint)
 _sig("kf_chain_debug_exchange_sys", None, _vp, C.c_int)
 _sig("kf_chain_debug_den_pairs", None, _vp, C.c_int)
@@ -209,6 +214,21 @@ class Chain:
         if core.kf_chain_result(self.h, C.byref(r)) != 0:
             _raise("kf_chain_result")
         return r
+
+    def xent(self, num: NumBatch, xent_ptr, ldx, grad_ptr, ldg, opts: KfChainOpts | None = None):
+        """kf_chain_xent: after compute() with the same num and opts, the loss gradient at the
+        affine output of the log-softmax xent output (fp16 rows at xent_ptr, leading dimension
+        ldx) into grad_ptr (leading dimension ldg), scaled by opts.xent_regularize."""
+        opts = opts or KfChainOpts.default()
+        if core.kf_chain_xent(self.h, num.h, C.byref(opts), xent_ptr, ldx, grad_ptr, ldg) != 0:
+            _raise("kf_chain_xent")
+
+    def xent_result(self):
+        """(xent objective, total weight) of the last xent(); synchronises."""
+        o, w = C.c_double(), C.c_double()
+        if core.kf_chain_xent_result(self.h, C.byref(o), C.byref(w)) != 0:
+            _raise("kf_chain_xent_result")
+        return o.value, w.value
 
     def debug_spin_limit(self, polls: int | None):
         """Test knob: polls before a den exchange wait gives up (None: default)."""

@@ -7,6 +7,9 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
      (chain_loss.go:221-294)         frame_offset + left_context + k * subsampling for
                                      k < frames_per_seq, cut where the eg ends
   3. Backward                     -> Network.backward (seeded at the chain output)
+  2a/3b. (TrainConfig.xent_regularize) -> Chain.xent after the objective, then Network.backward with
+                                     both seeds: Kaldi's --chain.xent-regularize, which trains the
+                                     output-xent branch on the numerator posteriors
   4. optimizer.Update per tensor  -> Network.sgd over the flat buffer (optimize.go:95-142),
                                      or with TrainConfig.kaldi_update Network.update: Kaldi's
                                      per-component max-change, L2 and learning-rate factors
@@ -87,6 +90,13 @@ class TrainConfig:
     # through them, and the accumulators start from zero (Kaldi's ZeroComponentStats);
     # EgsTrainer.commit_batchnorm() makes them the frozen statistics. False: frozen, as before.
     batchnorm_train: bool = False
+    # xent_regularize: Kaldi's --chain.xent-regularize (the recipes use 0.1). > 0: the
+    # value goes into the objective's options, Chain.xent writes the output-xent layer's gradient
+    # from the numerator posteriors and the backward takes both seeds; result() then also
+    # carries xent_objf and xent_weight. The recipes' learning-rate-factor of the xent layers
+    # (0.5 / xent_regularize) is the xconfig key learning-rate-factor, honoured by kaldi_update.
+    # 0: the trainer makes exactly the calls it made before.
+    xent_regularize: float = 0.0
 
 
 def parse_dropout_schedule(schedule: str):
@@ -167,6 +177,18 @@ class EgsTrainer:
         self.ivec = DeviceBuffer(max_egs * self.ivec_dim * 2) if self.ivec_dim else None
         self.max_egs = max_egs
         self.steps = 0  # steps taken
+        self.xent_grad = None
+        if self.cfg.xent_regularize > 0:
+            dims = {n: dout for n, _ty, _din, dout in self.net.layers}
+            if dims.get("output-xent") != self.P:
+                raise ValueError("xent_regularize needs an output-xent layer as wide as the chain output")
+            o = self.cfg.opts or _chain.KfChainOpts.default()
+            self.opts = _chain.KfChainOpts(o.l2_regularize, o.out_of_range_regularize, o.leaky_hmm_coefficient,
+                                           float(self.cfg.xent_regularize), o.supervision_weight)
+            self.xent_ptr = self.net.activation("output-xent")[0]
+            self.xent_grad = DeviceBuffer(max_frames * self.P * 2)
+        else:
+            self.opts = self.cfg.opts
         if self.cfg.natural_gradient:
             self.net.set_natural_gradient(True)
         if self.cfg.dropout_schedule:
@@ -196,6 +218,8 @@ class EgsTrainer:
             batch.features_to_device(self.feat.ptr, 40)
         # rows the objective does not write must be zero for this batch
         core.bridge_gpu_memset(self.grad_out.ptr, 0, T * self.P * 2)
+        if self.xent_grad is not None:
+            core.bridge_gpu_memset(self.xent_grad.ptr, 0, T * self.P * 2)
         seq = np.append(np.asarray(batch.frame_offsets, np.int32), np.int32(T))
         if self.cfg.dropout_schedule:
             if fraction is None:
@@ -213,9 +237,13 @@ class EgsTrainer:
         row0, frames = chain_rows(batch.frame_offsets, batch.num_frames, batch.frames_per_seq,
                                   self.cfg.subsampling_factor, self.cfg.left_context)
         self.objective.compute(num, self.out_ptr, self.P, T, row0, frames, self.cfg.subsampling_factor,
-                               self.grad_out.ptr, self.P, self.cfg.opts)
+                               self.grad_out.ptr, self.P, self.opts)
         self._num = num  # kept alive until the stream has consumed it
-        self.net.backward(self.grad_out.ptr)
+        if self.xent_grad is not None:
+            self.objective.xent(num, self.xent_ptr, self.P, self.xent_grad.ptr, self.P, self.opts)
+            self.net.backward(self.grad_out.ptr, self.xent_grad.ptr)
+        else:
+            self.net.backward(self.grad_out.ptr)
         if allreduce is not None:
             allreduce()
         if self.cfg.kaldi_update:
@@ -228,8 +256,13 @@ class EgsTrainer:
             self.net.constrain_orthonormal()
 
     def result(self):
+        """The objective's KfChainResult of the last step; with xent_regularize > 0 it also has
+        the attributes xent_objf and xent_weight (Chain.xent_result)."""
         sync()
-        return self.objective.result()
+        r = self.objective.result()
+        if self.xent_grad is not None:
+            r.xent_objf, r.xent_weight = self.objective.xent_result()
+        return r
 
     def commit_batchnorm(self) -> int:
         """Network.batchnorm_commit: the accumulated statistics of the training-mode BatchNorms

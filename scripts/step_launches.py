@@ -17,7 +17,7 @@ import numpy as np  # noqa: E402
 import kfp16  # noqa: E402
 from kfp16 import synth  # noqa: E402
 
-CLS = {0: "fused", 1: "wgrad", 2: "num", 3: "den", 4: "halo", 5: "cwgrad", 6: "reduce"}
+CLS = {0: "fused", 1: "wgrad", 2: "num", 3: "den", 4: "halo", 5: "cwgrad", 6: "reduce", 7: "xent"}
 
 
 def main():
