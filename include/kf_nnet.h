@@ -283,28 +283,51 @@ long long nnet_spec_augment_step(const KfNet *net);
  * host int32 [T] (NULL: only T). An error when that forward drew none for it. */
 int nnet_spec_augment_rows(KfNet *net, const char *layer, int32_t *host, int *T);
 
-/* Training-mode BatchNorm (default off): Kaldi's BatchNormComponent in training
- * mode for the BatchNorms the switch governs, today BatchNorm 0 of every tdnnf-layer
- * (nnet_bn_train_layers: their layer indices; returns their number). While it is on, each
- * nnet_forward normalises such a layer by the statistics of its own rows (all rows the layer
- * computes, every frame once; kf_ops.h kf_bn_train_stats), nnet_backward differentiates through
- * them, and the layer accumulates count, sum and sumsq in double. The frozen statistics
- * (nnet_set_bn) are untouched and apply again when the switch is off. The other BatchNorms
- * (conv-relu-batchnorm, prefinal, attention, batchnorm-component) stay frozen.
- *   nnet_bn_batch_stats: mean / var [out_dim] of the last forward (fp32; either may be NULL).
- *   nnet_bn_stats: the accumulators (count; sum, sumsq [out_dim]; any may be NULL).
+/* Training-mode BatchNorm (default off): Kaldi's BatchNormComponent in
+ * training mode for the BatchNorms the switch governs (nnet_bn_train_layers: their layer indices
+ * in layer order, a prefinal layer once; returns their number). Which kinds of layer those are is
+ * nnet_set_bn_train_sites' mask of
+ *   KF_BN_SITE_TDNNF      BatchNorm 0 of every tdnnf-layer (the default, alone),
+ *   KF_BN_SITE_CONV       every conv-relu-batchnorm-layer: block-dim = num-filters-out, the
+ *                         statistics of a filter run over rows x height-out,
+ *   KF_BN_SITE_PREFINAL   both BatchNorms of every prefinal-layer (0: big-dim, behind the ReLU;
+ *                         1: small-dim, no ReLU), prefinal-xent included,
+ *   KF_BN_SITE_COMPONENT  every batchnorm-component (a per-sequence one, ivector-batchnorm, over
+ *                         its B rows),
+ * KF_BN_SITE_ALL for Kaldi's behaviour; nnet_bn_train_sites reads it. The setter is refused while
+ * the switch is on and governs a layer (set while it governed none, the switch goes on for the new
+ * sites). The attention layer's BatchNorm is fused into its kernel and stays frozen.
+ * While the switch is on, each nnet_forward normalises a governed BatchNorm by the statistics of
+ * its own rows (all rows the layer computes, every frame once; kf_ops.h kf_bn_train_stats,
+ * kf_bn_block_stats), nnet_backward differentiates through them, and the BatchNorm accumulates
+ * count, sum and sumsq in double. The frozen statistics (nnet_set_bn) are untouched and apply
+ * again when the switch is off. Storage for a site (its r tensor: a conv layer's is as large as
+ * its activation) is made the first time the switch goes on with the site selected.
+ *   nnet_bn_dim: the length of a BatchNorm's statistics: num-filters-out for conv, big-dim /
+ *     small-dim for prefinal `which` 0 / 1, out_dim otherwise; -1 when the layer has none.
+ *   nnet_bn_batch_stats: mean / var [nnet_bn_dim] of the last forward (fp32; either may be NULL).
+ *   nnet_bn_stats: the accumulators (count; sum, sumsq [nnet_bn_dim]; any may be NULL).
  *   nnet_bn_zero_stats: clears them (Kaldi's ZeroComponentStats at the start of a job).
- *   nnet_bn_commit: every governed layer with count > 0 takes mean = sum / count,
+ *   nnet_bn_commit: every governed BatchNorm with count > 0 takes mean = sum / count,
  *     var = sumsq / count - mean^2 (floored at 0) as its frozen statistics through nnet_set_bn
- *     (gamma 1, beta 0, the layer's eps and target_rms); returns the layers committed, -1 on error.
- * `which` is the BatchNorm index of nnet_set_bn (1: prefinal-layer's second one; only 0 of a
- * tdnnf-layer is governed today). Composes with dropout, SpecAugment, natural gradient,
- * nnet_update and the orthonormal constraint. Refused, in either order of the two calls: MXFP8
- * mode (nnet_set_fp8), implicit dz, row subsampling (the compact row set's scratch row and
- * inexact tail rows are not rows of the layer), a bound data-parallel communicator (the
- * statistics would be each rank's own), and nnet_backward_n. */
+ *     (gamma 1, beta 0, its own eps and target_rms); returns the layers committed, -1 on error.
+ * `which` is the BatchNorm index of nnet_set_bn (1: prefinal-layer's second one). Composes with
+ * dropout, SpecAugment, natural gradient, nnet_update, the orthonormal constraint and
+ * nnet_backward_xent. Refused, in either order of the two calls: MXFP8 mode (nnet_set_fp8),
+ * implicit dz, row subsampling (the compact row set's scratch row and inexact tail rows are not
+ * rows of the layer), a bound data-parallel communicator (the statistics would be each rank's
+ * own), and nnet_backward_n. With KF_BN_SITE_COMPONENT, a frame-level batchnorm-component above
+ * a trainable layer is refused by nnet_set_bn_train (none of the recipes has one). */
+#define KF_BN_SITE_TDNNF 1
+#define KF_BN_SITE_CONV 2
+#define KF_BN_SITE_PREFINAL 4
+#define KF_BN_SITE_COMPONENT 8
+#define KF_BN_SITE_ALL 15
 int nnet_set_bn_train(KfNet *net, int on);
+int nnet_set_bn_train_sites(KfNet *net, int sites);
+int nnet_bn_train_sites(const KfNet *net);
 int nnet_bn_train_layers(const KfNet *net, int *idx, int n);
+int nnet_bn_dim(const KfNet *net, const char *layer, int which);
 int nnet_bn_batch_stats(KfNet *net, const char *layer, int which, float *mean, float *var);
 int nnet_bn_stats(KfNet *net, const char *layer, int which, double *count, double *sum, double *sumsq);
 int nnet_bn_zero_stats(KfNet *net);

@@ -497,7 +497,18 @@ int kf_specaug_apply(const void *x, long long ldx, void *y, long long ldy, long 
  * kf_bn_train_bwd_apply: dz = rne_fp16(scale (dy - a - yhat b) relu_bit), the exact derivative
  *   through the batch statistics (eps included: scale carries it), Kaldi's
  *   BatchNormComponent::Backprop; evaluated in double. relu_bit is bit (row ld_mask + c) of the
- *   forward's ReLU mask (ld_mask in bits, a multiple of 8). dz may not alias g or r. */
+ *   forward's ReLU mask (ld_mask in bits, a multiple of 8); mask == NULL: a BatchNorm with no ReLU
+ *   below it, relu_bit = 1 (ld_mask ignored). dz may not alias g or r.
+ *
+ * Block statistics: a BatchNorm with block-dim = F on r [rows x H F], where column
+ * h F + f belongs to block f (a conv layer: H = height-out, F = num-filters-out) and every sum runs
+ * over the n = rows H block rows. F % 8 == 0, H >= 1, ld >= H F, ld % 8 == 0, rows <= 65535 x 64;
+ * outputs and accumulators are [F] (count [1], += n). The rule, the double sums in a fixed order
+ * and the two launches are kf_bn_train_stats' / kf_bn_train_bwd_stats' (no dropout table); the lane
+ * map is made for the tall, narrow case: a lane keeps 8 columns of one block for its whole walk,
+ * the lanes of a workgroup share 64 tensor rows, a second launch adds the workgroups' partials
+ * with 32 lanes per column. The apply entries above serve a dense r through its [rows H x F],
+ * ld = F view. */
 int kf_bn_train_stats(const void *r, long long ld, int rows, int D, float eps, float target_rms, float *mean,
                       float *var, float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq);
 int kf_bn_train_apply(const void *r, long long ld, int rows, int D, const float *scale, const float *shift,
@@ -510,6 +521,10 @@ int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r, long long
                           const float *scale, const float *shift, float target_rms, const float *a, const float *b,
                           const float *drop, long long ld_drop, const int32_t *row_seg, const uint8_t *mask,
                           long long ld_mask, void *dz, long long lddz);
+int kf_bn_block_stats(const void *r, long long ld, int rows, int H, int F, float eps, float target_rms, float *mean,
+                      float *var, float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq);
+int kf_bn_block_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int H, int F,
+                          const float *scale, const float *shift, float target_rms, float *a, float *b);
 
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.

@@ -88,11 +88,23 @@ bool dx_epilogue(KfNet *net, int P, void *dz_out, void *g_out, KfEpilogue &E, bo
             return true;
         }
         case LayerType::ConvReluBN:
+            if (pl.bnt_act) {
+                // training-mode BatchNorm: the raw g only, through out2 (every conv
+                // input-gradient path writes there) into the g ring; P's own step makes dz of it
+                // in the ring slot left unwritten here (BackwardPass::conv)
+                E.out2 = g_out;
+                return true;
+            }
+            [[fallthrough]];
         case LayerType::Attention:
             E.scale2 = pl.bn_scale;
             E.mask_in = pl.mask;
             return true;
         case LayerType::Prefinal:
+            if (pl.bnt_act && pl.has_bn2) {  // as for conv: BatchNorm 1's backward is P's own step's
+                E.out2 = g_out;
+                return true;
+            }
             if (pl.has_bn2) E.scale2 = pl.bn2_scale;
             return true;
         case LayerType::Batchnorm:
@@ -299,6 +311,9 @@ struct BackwardPass {
     bool linear(Step &s), attention(Step &s), prefinal(Step &s), combine(Step &s), tdnnf(Step &s), conv(Step &s);
     KfOperand masked(const Step &s, const Tdnnf &t, KfOperand o) const;
     bool bn_train_dz(Step &s, int ib);
+    bool bn_site_dz(const void *g, const void *r, int rows, int H, int F, const float *stat, float rms, const uint8_t *mask,
+                    void *dz_out, const std::string &what);
+    void *bn_site_slot(const NetLayer &nl);
     bool tdnnf_affine_wgrad(Step &s, const Tdnnf &t), tdnnf_affine_dgrad(Step &s, const Tdnnf &t);
     bool tdnnf_affine_dgrad_mx(Step &s, const Tdnnf &t, const KfEpilogue &E1, void *edge);
     bool tdnnf_linear_wgrad(Step &s, const Tdnnf &t), tdnnf_linear_dgrad(Step &s, const Tdnnf &t);
@@ -618,6 +633,15 @@ bool BackwardPass::attention(Step &s) {
 bool BackwardPass::prefinal(Step &s) {
     NetLayer &nl = s.nl;
     const int T = s.T, din = nl.L.in_dim, big = nl.L.big_dim, small = nl.L.small_dim;
+    // training-mode BatchNorm: the layer above left the raw g; BatchNorm 1 has no
+    // ReLU below it, so its dz takes no mask
+    const bool bnt = nl.bnt_act;
+    if (bnt && nl.has_bn2) {
+        void *slot = bn_site_slot(nl);
+        if (!slot || !bn_site_dz(gcur, nl.bnt_r2, T, 1, small, nl.bnt_stat2, nl.bn2_rms, nullptr, slot,
+                                 "prefinal " + nl.L.name + " (small)"))
+            return false;
+    }
     KfOperand A = op_base(nl.aux, big, T, big, 0);
     KfOperand B = op_base(dz, small, T, small, 0);
     if (!wgrad([&] {
@@ -633,9 +657,21 @@ bool BackwardPass::prefinal(Step &s) {
     E1.ldo2 = big;
     E1.scale2 = nl.bn_scale;
     E1.mask_in = nl.mask;
+    // training mode: the raw gradient at aux into this step's g slot (nothing else is in it until
+    // the step's last GEMM, on this stream; the ring's wait for its earlier readers comes first),
+    // then BatchNorm 0's backward through the ReLU mask into dzbig
+    void *const gbig = s.g_next;
+    if (bnt) {
+        if (!dx_wait()) return false;
+        E1.out2 = gbig;
+        E1.scale2 = nullptr;
+        E1.mask_in = nullptr;
+    }
     KfOperand A1 = op_base(dz, small, T, small, 1);
     KfOperand B1 = op_base(wptr(net, nl.pW2), small, big, small, 1);
     if (!ck(kf_gemm_fused(T, big, small, &A1, &B1, &E1), "prefinal small dgrad")) return false;
+    if (bnt && !bn_site_dz(gbig, nl.bnt_r, T, 1, big, nl.bnt_stat, nl.bn_rms, nl.mask, dzbig, "prefinal " + nl.L.name + " (big)"))
+        return false;
     KfOperand A3 = op_base(s.x, din, T, din, 0);
     KfOperand B3 = op_base(dzbig, big, T, big, 0);
     if (!wgrad([&] {
@@ -663,14 +699,23 @@ bool BackwardPass::combine(Step &s) {
         if (!ck(kf_combine_feature_maps_backward(dz, L.out_dim, net->seq_off, rowsB, nl.gdb, wb, L.height, L.nf1, L.nf2),
                 "combine backward"))
             return false;
+        const void *gq = nl.gdb;  // the per-sequence gradient on its way down the branch
         for (int cur = nl.input2; cur >= 0; cur = net->layers[cur].input) {
             NetLayer &q = net->layers[cur];
             const int qd = q.L.out_dim;
-            if (q.L.type == LayerType::Batchnorm) {
-                if (!ck(kf_scale_cols(nl.gdb, qd, q.bn_scale, nl.gdb, qd, rowsB, qd), "ivector bn backward")) return false;
+            if (q.L.type == LayerType::Batchnorm && q.bnt_act) {
+                // training-mode BatchNorm over the B rows: its dz into the layer's own
+                // buffer (the apply may not write over g)
+                if (!bn_site_dz(gq, act_of(net, q.input), rowsB, 1, qd, q.bnt_stat, q.bn_rms, nullptr, q.bnt_r,
+                                "batchnorm-component " + q.L.name))
+                    return false;
+                gq = q.bnt_r;
+            } else if (q.L.type == LayerType::Batchnorm) {
+                if (!ck(kf_scale_cols(gq, qd, q.bn_scale, nl.gdb, qd, rowsB, qd), "ivector bn backward")) return false;
+                gq = nl.gdb;
             } else if (q.L.type == LayerType::Linear) {
                 if (!wgrad([&] {
-                        return ck(kf_rows_wgrad(act_of(net, q.input), q.L.in_dim, nl.gdb, qd, gptr(net, q.pW), qd, rowsB,
+                        return ck(kf_rows_wgrad(act_of(net, q.input), q.L.in_dim, gq, qd, gptr(net, q.pW), qd, rowsB,
                                                 q.L.in_dim, qd),
                                   "ivector linear wgrad");
                     }))
@@ -746,6 +791,34 @@ bool BackwardPass::bn_train_dz(Step &s, int ib) {
            ck(kf_bn_train_bwd_apply(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
                                     net->dz[ib], D),
               "tdnnf batchnorm backward apply");
+}
+
+// Training-mode BatchNorm backward of a conv, prefinal or batchnorm-component site:
+// a, b over g and r [rows x H F] (block f = column h F + f), then dz = scale (g - a - yhat b)
+// relu_bit through the dense [rows H x F] view, on the chain stream. mask NULL: no ReLU below the
+// BatchNorm. One a | b pair serves every site: the chain stream runs them in order.
+bool BackwardPass::bn_site_dz(const void *g, const void *r, int rows, int H, int F, const float *stat, float rms,
+                              const uint8_t *mask, void *dz_out, const std::string &what) {
+    if (!g || !r || !stat || !dz_out || g == dz_out || F > net->bnt_w || !kf_bn_train_bwd_stats || !kf_bn_train_bwd_apply ||
+        (H > 1 && !kf_bn_block_bwd_stats)) {
+        set_err("backward: training-mode BatchNorm of " + what + " got no stored output gradient");
+        return false;
+    }
+    const float *sc = stat + 2 * F, *sh = stat + 3 * F;
+    float *a = net->bnt_ab, *b = net->bnt_ab + net->bnt_w;
+    const int rc = H == 1 ? kf_bn_train_bwd_stats(g, F, r, F, rows, F, sc, sh, rms, nullptr, 0, nullptr, a, b)
+                          : kf_bn_block_bwd_stats(g, (long long)H * F, r, (long long)H * F, rows, H, F, sc, sh, rms, a, b);
+    return ck(rc, (what + " batchnorm backward statistics").c_str()) &&
+           ck(kf_bn_train_bwd_apply(g, F, r, F, rows * H, F, sc, sh, rms, a, b, nullptr, 0, nullptr, mask, F, dz_out, F),
+              (what + " batchnorm backward apply").c_str());
+}
+// the ring slot a governed layer's dz goes to: the one its producer's epilogue left unwritten
+// (dx_epilogue stored the raw g beside it), or NULL when the step was not seeded that way
+void *BackwardPass::bn_site_slot(const NetLayer &nl) {
+    const int ib = dz_index(net, dz);
+    if (ib >= 0 && gcur != dz) return net->dz[ib];
+    set_err("backward: training-mode BatchNorm of " + nl.L.name + " got no stored output gradient");
+    return nullptr;
 }
 
 KfOperand BackwardPass::masked(const Step &s, const Tdnnf &t, KfOperand o) const {
@@ -884,6 +957,13 @@ bool BackwardPass::conv(Step &s) {
     NetLayer &nl = s.nl;
     const Layer &L = nl.L;
     const bool compact = conv_compact(net, s.li);
+    // training-mode BatchNorm: the layer above left the raw g; per filter a, b over
+    // rows x height-out, then dz into the ring slot, before anything below reads dz
+    if (nl.bnt_act) {
+        void *slot = bn_site_slot(nl);
+        if (!slot || !bn_site_dz(gcur, nl.bnt_r, s.T, L.hout, L.fout, nl.bnt_stat, nl.bn_rms, nl.mask, slot, "conv " + L.name))
+            return false;
+    }
     // compact-row conv: the tail window runs first, on the weight-gradient stream beside
     // the residue GEMMs (conv_window)
     if (s.want_dx && compact && net->rs.nt > 0 && two && s.E.out2 && !conv_window(s, true)) return false;
@@ -1209,6 +1289,8 @@ extern "C" const void *nnet_debug_tensor(KfNet *net, const char *what, int layer
     if (w == "mask") return net->layers[layer].mask;
     if (w == "bn_scale") return net->layers[layer].bn_scale;
     if (w == "bn2_scale") return net->layers[layer].bn2_scale;
+    if (w == "bn_shift") return net->layers[layer].bn_shift;
+    if (w == "bn2_shift") return net->layers[layer].bn2_shift;
     // the e4m3 affine weight rows of the MXFP8 input gradient, [bn x 2*pad128(out)]
     if (w == "w8dq") return net->layers[layer].w8d.q;
     if (w == "w8ds") return net->layers[layer].w8d.s;

@@ -49,6 +49,31 @@ KfEpilogue epi_relu_bn(KfNet *net, NetLayer &nl, int pb, long long ldo) {
     return E;
 }
 
+// Training-mode BatchNorm of a governed site: the batch statistics of r [rows x H F]
+// (block f = column h F + f; H = 1: the column entries), then r scale + shift into out through the
+// dense [rows H x F] view. stat = mean | var | scale | shift, acc = count (2) | sum | sumsq.
+bool bnt_normalise(const void *r, int rows, int H, int F, float eps, float rms, float *stat, double *acc, void *out,
+                   const std::string &what) {
+    // (H = 1, a prefinal layer or a batchnorm-component: wide rows, the column entry's lane map)
+    const int rc = H == 1 ? kf_bn_train_stats(r, F, rows, F, eps, rms, stat, stat + F, stat + 2 * F, stat + 3 * F, acc, acc + 2,
+                                              acc + 2 + F)
+                          : kf_bn_block_stats(r, (long long)H * F, rows, H, F, eps, rms, stat, stat + F, stat + 2 * F,
+                                              stat + 3 * F, acc, acc + 2, acc + 2 + F);
+    return ck(rc, (what + " batchnorm statistics").c_str()) &&
+           ck(kf_bn_train_apply(r, F, rows * H, F, stat + 2 * F, stat + 3 * F, nullptr, 0, nullptr, nullptr, 0, 0.f, out, F),
+              (what + " batchnorm apply").c_str());
+}
+bool bnt_conv(NetLayer &nl, int T) {
+    return bnt_normalise(nl.bnt_r, T, nl.L.hout, nl.L.fout, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.act, "conv");
+}
+// the epilogue of a governed conv / prefinal affine: r and the ReLU mask, no scale or shift
+KfEpilogue epi_relu_r(KfNet *net, NetLayer &nl, int pb, long long ldo) {
+    KfEpilogue E = epi_relu_bn(net, nl, pb, ldo);
+    E.out = nl.bnt_r;
+    E.scale = E.shift = nullptr;
+    return E;
+}
+
 bool fwd_combine(KfNet *net, NetLayer &nl, const void *x, int T) {
     const Layer &L = nl.L;
     if (nl.input2 != -100) {  // Append(a, b): b broadcast per sequence when per_seq
@@ -73,8 +98,8 @@ bool fwd_conv_small_fin(KfNet *net, NetLayer &nl, const void *x, int T) {
         return false;
     KfOperand A = op_base(nl.im2col, nl.kp, T * L.hout, nl.kp, 1);
     KfOperand B = op_base(nl.wpad, L.fout, nl.kp, L.fout, 0);
-    KfEpilogue E = epi_relu_bn(net, nl, nl.pb, L.fout);
-    return ck(kf_gemm_fused(T * L.hout, L.fout, nl.kp, &A, &B, &E), "conv small fin");
+    KfEpilogue E = nl.bnt_act ? epi_relu_r(net, nl, nl.pb, L.fout) : epi_relu_bn(net, nl, nl.pb, L.fout);
+    return ck(kf_gemm_fused(T * L.hout, L.fout, nl.kp, &A, &B, &E), "conv small fin") && (!nl.bnt_act || bnt_conv(nl, T));
 }
 
 // The conv below the compact layers on the compact rows: output frames 3c (c < Tc0), and
@@ -114,6 +139,11 @@ bool fwd_conv_compact(KfNet *net, NetLayer &nl, int K, KfOperand A, const KfOper
 bool fwd_conv(KfNet *net, int li, const void *x, int T) {
     NetLayer &nl = net->layers[li];
     const Layer &L = nl.L;
+    if (L.fin == 1 && nl.bnt_act)  // (no scale: the kernel stores r = relu(conv + bias))
+        return ck(kf_conv_c1_forward(T, L.hin, L.hout, L.hsub, L.fout, (int)nl.dt.size(), nl.dt.data(), nl.dh.data(), x,
+                                     wptr(net, nl.pW), wptr(net, nl.pb), nullptr, nullptr, nl.bnt_r, nl.mask),
+                  "conv c1") &&
+               bnt_conv(nl, T);
     if (L.fin == 1)
         return ck(kf_conv_c1_forward(T, L.hin, L.hout, L.hsub, L.fout, (int)nl.dt.size(), nl.dt.data(), nl.dh.data(), x,
                                      wptr(net, nl.pW), wptr(net, nl.pb), nl.bn_scale, nl.bn_shift, nl.act, nl.mask),
@@ -125,6 +155,10 @@ bool fwd_conv(KfNet *net, int li, const void *x, int T) {
     KfEpilogue E = epi_relu_bn(net, nl, nl.pb, L.fout);
     if (net->fp8 && nl.a8.q) set_out8(E, nl.a8), E.ldo8 = L.fout;  // rows (t,h) of fout: the [t x hout*fout] copy
     if (conv_compact(net, li)) return fwd_conv_compact(net, nl, K, A, B, E);
+    if (nl.bnt_act) {  // (row subsampling and MXFP8 are refused with the mode: full rows, no out8)
+        KfEpilogue Er = epi_relu_r(net, nl, nl.pb, L.fout);
+        return ck(kf_gemm_fused(T * L.hout, L.fout, K, &A, &B, &Er), "conv") && bnt_conv(nl, T);
+    }
     return ck(kf_gemm_fused(T * L.hout, L.fout, K, &A, &B, &E), "conv");
 }
 
@@ -248,6 +282,21 @@ bool fwd_prefinal(KfNet *net, int li, const void *x) {
     KfOperand B = x8      ? op_mxw(nl.w8, big)
                   : nl.wt ? op_base(nl.wt, din, big, din, 1)
                           : op_base(wptr(net, nl.pW), big, din, big, 0);
+    if (nl.bnt_act) {
+        // training-mode BatchNorm: r_big -> statistics -> aux, then the linear output
+        // r_small -> statistics -> act (no BatchNorm 1: the linear output is the activation)
+        KfEpilogue Er = epi_relu_r(net, nl, nl.pb, big);
+        KfOperand A2 = op_base(nl.aux, big, T, big, 1);
+        KfOperand B2 = op_base(wptr(net, nl.pW2), small, big, small, 0);
+        KfEpilogue E2 = epi0();
+        E2.out = nl.has_bn2 ? nl.bnt_r2 : nl.act;
+        E2.ldo = small;
+        return ck(kf_gemm_fused(T, big, din, &A, &B, &Er), "prefinal big") &&
+               bnt_normalise(nl.bnt_r, T, 1, big, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.aux, "prefinal big") &&
+               ck(kf_gemm_fused(T, small, big, &A2, &B2, &E2), "prefinal small") &&
+               (!nl.has_bn2 || bnt_normalise(nl.bnt_r2, T, 1, small, nl.bn2_eps, nl.bn2_rms, nl.bnt_stat2, nl.bnt_acc2, nl.act,
+                                             "prefinal small"));
+    }
     KfEpilogue E = epi_relu_bn(net, nl, nl.pb, big);
     E.out = nl.aux;
     if (net->fp8) set_out8(E, nl.x8);
@@ -273,6 +322,9 @@ bool fwd_layer(KfNet *net, int li, const void *x, int T) {
         case LayerType::IDCT:
             return ck(kf_small_gemm(x, L.in_dim, nl.idct, nl.act, L.out_dim, T, L.in_dim, L.out_dim), "idct");
         case LayerType::Batchnorm:
+            if (nl.bnt_act)  // (the statistics of the input itself; a per-sequence layer's rows are the sequences)
+                return bnt_normalise(x, nl.per_seq ? net->B : T, 1, L.out_dim, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc,
+                                     nl.act, "batchnorm");
             return ck(kf_bn_apply(x, nl.act, nl.per_seq ? net->B : T, L.out_dim, nl.bn_scale, nl.bn_shift), "batchnorm");
         case LayerType::SpecAugment:
             // inactive: the alias of its input (forward.go:225-231 passes through). Active: the
@@ -408,7 +460,11 @@ bool bnt_prepare(KfNet *net) {
         set_err("forward: this build of libkaldi_fp16 has no training-mode BatchNorm kernels");
         return false;
     }
-    for (int li : net->bnt_layers) net->layers[li].bnt_act = net->layers[li].bnt_r != nullptr;
+    if ((net->bnt_sites & KF_BN_SITE_CONV) && !kf_bn_block_stats) {
+        set_err("forward: this build of libkaldi_fp16 has no block BatchNorm kernels");
+        return false;
+    }
+    for (int li : net->bnt_layers) net->layers[li].bnt_act = net->layers[li].bnt_stat != nullptr;
     return true;
 }
 

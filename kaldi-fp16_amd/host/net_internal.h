@@ -43,6 +43,8 @@ KF_HIDDEN void set_err(const std::string &s);
 #pragma weak kf_bn_train_apply
 #pragma weak kf_bn_train_bwd_stats
 #pragma weak kf_bn_train_bwd_apply
+#pragma weak kf_bn_block_stats
+#pragma weak kf_bn_block_bwd_stats
 
 struct ParamRef {
     std::string name;
@@ -119,10 +121,19 @@ struct NetLayer {
     // each; bn_scale / bn_shift stay the frozen pair), the accumulators count (2 doubles, the
     // second unused) | sum | sumsq in double, all made when the mode is first switched on, and
     // whether the current forward normalised by its own statistics
+    // The other sites (nnet_set_bn_train_sites) use the same fields with the BatchNorm's
+    // own length (bnt_dim below): a conv layer's r is [max_T x height-out num-filters-out] and its
+    // statistics are num-filters-out long; a prefinal layer's r is big-dim wide and the *2 fields
+    // are its BatchNorm 1 (r2: the linear output, small-dim wide); a batchnorm-component's r is
+    // its input, and bnt_r holds the backward's dz instead (the per-sequence branch only: a
+    // frame-level one has no backward and no bnt_r).
     void *bnt_r = nullptr;
     float *bnt_stat = nullptr;
     double *bnt_acc = nullptr;
     bool bnt_act = false;
+    void *bnt_r2 = nullptr;
+    float *bnt_stat2 = nullptr;
+    double *bnt_acc2 = nullptr;
     // spec-augment-layer (kf_nnet.h nnet_set_spec_augment): the layer's ordinal among such layers
     // (-1: another kind), its options, the row_band [max_T] of its last active forward, and
     // whether the current forward masked (act is then the layer's own buffer, not the alias)
@@ -303,7 +314,9 @@ struct KfNet {
     // training-mode BatchNorm (kf_nnet.h nnet_set_bn_train): the layers the switch
     // governs (the tdnnf-layers), the switch, and the backward's a | b columns (fp32, the widest
     // governed layer's out_dim each; one pair: the chain stream runs the layers in order)
+    // bnt_sites: the kinds of layer the switch governs (KF_BN_SITE_*); bnt_layers follows it.
     std::vector<int> bnt_layers;
+    int bnt_sites = 1;  // KF_BN_SITE_TDNNF
     int bnt_on = 0;
     float *bnt_ab = nullptr;
     int bnt_w = 0;
@@ -318,6 +331,13 @@ struct KfNet {
         void *p = bridge_gpu_malloc(bytes ? bytes : 16);
         if (p) allocs.push_back(p);
         return p;
+    }
+    // gives a dalloc'ed block back before the net is closed (NULL: nothing)
+    void dfree(void *p) {
+        const auto it = std::find(allocs.begin(), allocs.end(), p);
+        if (!p || it == allocs.end()) return;
+        allocs.erase(it);
+        bridge_gpu_free(p);
     }
     ~KfNet() {
         if (wg_stream) bridge_gpu_sync();
@@ -464,6 +484,14 @@ inline bool drop_active(const KfNet *net) { return net->drop_on && !net->drop_la
 inline bool sa_active(const KfNet *net) { return net->sa_on && !net->sa_layers.empty(); }
 // training-mode BatchNorm is switched on and the network has a layer it governs (nnet_set_bn_train)
 inline bool bnt_active(const KfNet *net) { return net->bnt_on && !net->bnt_layers.empty(); }
+// the length of a layer's BatchNorm statistics (kf_nnet.h nnet_bn_dim): which = 1 is a prefinal
+// layer's second BatchNorm
+inline int bnt_dim(const NetLayer &nl, int which) {
+    const Layer &L = nl.L;
+    if (L.type == LayerType::ConvReluBN) return L.fout;
+    if (L.type == LayerType::Prefinal) return which ? L.small_dim : L.big_dim;
+    return L.out_dim;
+}
 // Z = min(D, floor(D f + 0.5)): the widest band of a spec-augment layer
 inline int sa_max_bins(const NetLayer &nl) {
     return std::min(nl.L.out_dim, (int)((double)nl.L.out_dim * nl.sa_f + 0.5));

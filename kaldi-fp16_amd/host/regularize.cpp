@@ -207,13 +207,42 @@ extern "C" int nnet_spec_augment_rows(KfNet *net, const char *layer, int32_t *ho
 }
 
 // ---------------------------------------------------------------------------
-// Training-mode BatchNorm of the TDNN-F layers (kf_nnet.h nnet_set_bn_train): the
+// Training-mode BatchNorm (kf_nnet.h nnet_set_bn_train): the sites, the
 // switch, the statistics and the commit. forward.cpp normalises by the batch statistics,
 // backward.cpp differentiates through them.
 // ---------------------------------------------------------------------------
-static NetLayer *bnt_layer(KfNet *net, const char *layer, int which, const char *what) {
-    NetLayer *nl = which == 0 ? find_layer(net, layer) : nullptr;
-    if (nl && std::count(net->bnt_layers.begin(), net->bnt_layers.end(), (int)(nl - net->layers.data()))) return nl;
+static int bnt_site_of(LayerType t) {
+    switch (t) {
+        case LayerType::TDNNF: return KF_BN_SITE_TDNNF;
+        case LayerType::ConvReluBN: return KF_BN_SITE_CONV;
+        case LayerType::Prefinal: return KF_BN_SITE_PREFINAL;
+        case LayerType::Batchnorm: return KF_BN_SITE_COMPONENT;
+        default: return 0;  // (the attention layer's BatchNorm is fused into its kernel: never governed)
+    }
+}
+
+// a governed BatchNorm's storage: r, the statistics and the accumulators (NULL: `which` is not one
+// of the layer's BatchNorms)
+struct BntSlot {
+    void **r;
+    float **stat;
+    double **acc;
+    int dim;
+    float eps, rms;
+};
+static bool bnt_slot(NetLayer &nl, int which, BntSlot &s) {
+    const bool pre = nl.L.type == LayerType::Prefinal;
+    if (which < 0 || which > (pre && nl.has_bn2 ? 1 : 0)) return false;
+    if (which) s = BntSlot{&nl.bnt_r2, &nl.bnt_stat2, &nl.bnt_acc2, bnt_dim(nl, 1), nl.bn2_eps, nl.bn2_rms};
+    else s = BntSlot{&nl.bnt_r, &nl.bnt_stat, &nl.bnt_acc, bnt_dim(nl, 0), nl.bn_eps, nl.bn_rms};
+    return true;
+}
+
+static NetLayer *bnt_layer(KfNet *net, const char *layer, int which, const char *what, BntSlot &slot) {
+    NetLayer *nl = find_layer(net, layer);
+    if (nl && std::count(net->bnt_layers.begin(), net->bnt_layers.end(), (int)(nl - net->layers.data())) &&
+        bnt_slot(*nl, which, slot))
+        return nl;
     set_err(std::string(what) + ": training-mode BatchNorm (nnet_set_bn_train) does not govern BatchNorm '" +
             std::to_string(which) + "' of layer " + (layer ? layer : "(null)"));
     return nullptr;
@@ -221,6 +250,60 @@ static NetLayer *bnt_layer(KfNet *net, const char *layer, int which, const char 
 
 extern "C" int nnet_bn_train_layers(const KfNet *net, int *idx, int n) {
     return net ? list_get(net->bnt_layers, idx, n) : -1;
+}
+
+extern "C" int nnet_bn_train_sites(const KfNet *net) { return net ? net->bnt_sites : -1; }
+
+extern "C" int nnet_set_bn_train_sites(KfNet *net, int sites) {
+    if (!net) return -1;
+    if (sites < 0 || (sites & ~KF_BN_SITE_ALL)) {
+        set_err("set_bn_train_sites: sites=" + std::to_string(sites) + " is not a mask of KF_BN_SITE_*");
+        return -1;
+    }
+    if (bnt_active(net)) {
+        set_err("set_bn_train_sites: not supported with training-mode BatchNorm on (nnet_set_bn_train): switch it off first");
+        return -1;
+    }
+    auto apply = [net](int m) {
+        net->bnt_sites = m;
+        net->bnt_layers.clear();
+        for (size_t i = 0; i < net->layers.size(); ++i) {
+            net->layers[i].bnt_act = false;
+            if (bnt_site_of(net->layers[i].L.type) & m) net->bnt_layers.push_back((int)i);
+        }
+    };
+    const int old = net->bnt_sites;
+    apply(sites);
+    // the switch was set while it governed nothing (no such layer under the old sites): it now
+    // goes on for the new ones, with everything nnet_set_bn_train checks and allocates
+    if (net->bnt_on && !net->bnt_layers.empty()) {
+        net->bnt_on = 0;
+        if (nnet_set_bn_train(net, 1) != 0) {
+            apply(old);
+            net->bnt_on = 1;
+            return -1;
+        }
+    }
+    return 0;
+}
+
+extern "C" int nnet_bn_dim(const KfNet *net, const char *layer, int which) {
+    NetLayer *nl = find_layer(const_cast<KfNet *>(net), layer);
+    BntSlot slot;
+    if (nl && bnt_site_of(nl->L.type) && bnt_slot(*nl, which, slot)) return slot.dim;
+    if (nl && nl->L.type == LayerType::Attention && which == 0) return nl->L.out_dim;
+    set_err(std::string("bn_dim: no BatchNorm '") + std::to_string(which) + "' in layer " + (layer ? layer : "(null)"));
+    return -1;
+}
+
+// a frame-level batchnorm-component above a trainable layer: its backward is a scale folded into
+// the producing epilogue (backward.cpp dx_epilogue), which the batch statistics cannot be
+static const NetLayer *bnt_unsupported_component(const KfNet *net) {
+    for (int li : net->bnt_layers) {
+        const NetLayer &nl = net->layers[li];
+        if (nl.L.type == LayerType::Batchnorm && !nl.per_seq && nl.needs_dx) return &nl;
+    }
+    return nullptr;
 }
 
 extern "C" int nnet_set_bn_train(KfNet *net, int on) {
@@ -234,26 +317,53 @@ extern "C" int nnet_set_bn_train(KfNet *net, int on) {
         set_err("set_bn_train: this build of libkaldi_fp16 has no training-mode BatchNorm kernels");
         return -1;
     }
+    if ((net->bnt_sites & KF_BN_SITE_CONV) && (!kf_bn_block_stats || !kf_bn_block_bwd_stats)) {
+        set_err("set_bn_train: this build of libkaldi_fp16 has no block BatchNorm kernels");
+        return -1;
+    }
+    if (const NetLayer *bad = bnt_unsupported_component(net)) {
+        set_err("set_bn_train: batchnorm-component " + bad->L.name +
+                " lies above a trainable layer on the frame level; training mode is not supported there "
+                "(nnet_set_bn_train_sites without KF_BN_SITE_COMPONENT)");
+        return -1;
+    }
     int maxw = 0;
-    for (int li : net->bnt_layers) maxw = std::max(maxw, net->layers[li].L.out_dim);
-    if (!net->bnt_ab) {  // the first time: r, the batch statistics and the accumulators of every layer
-        for (int li : net->bnt_layers) {
-            NetLayer &nl = net->layers[li];
-            const size_t D = (size_t)nl.L.out_dim;
-            if (D % 8 || !nl.mask) {
+    for (int li : net->bnt_layers)
+        for (int which = 0; which < 2; ++which) {
+            BntSlot s;
+            if (bnt_slot(net->layers[li], which, s)) maxw = std::max(maxw, s.dim);
+        }
+    // the first time a layer is governed: r, the batch statistics and the accumulators
+    for (int li : net->bnt_layers) {
+        NetLayer &nl = net->layers[li];
+        for (int which = 0; which < 2; ++which) {
+            BntSlot s;
+            if (!bnt_slot(nl, which, s) || *s.stat) continue;
+            const size_t D = (size_t)s.dim;
+            const bool relu = nl.L.type != LayerType::Batchnorm && which == 0;
+            if (D % 8 || (relu && !nl.mask)) {
                 set_err("set_bn_train: layer " + nl.L.name + " needs out_dim % 8 == 0 and a ReLU mask");
                 return -1;
             }
-            nl.bnt_r = net->dalloc((size_t)net->max_T * D * 2);
-            nl.bnt_stat = (float *)net->dalloc(4 * D * 4);
-            nl.bnt_acc = (double *)net->dalloc((2 + 2 * D) * 8);
-            if (!nl.bnt_r || !nl.bnt_stat || !nl.bnt_acc) {
+            // r as wide as the tensor the BatchNorm sees (a conv layer: every height of it); a
+            // batchnorm-component reads its input in place: a per-sequence one keeps the backward's
+            // dz here (its rows are at most max_T), a frame-level one has no backward and no r
+            const size_t w = nl.L.type == LayerType::ConvReluBN ? (size_t)nl.L.out_dim : D;
+            const bool need_r = nl.L.type != LayerType::Batchnorm || nl.per_seq;
+            if (need_r) *s.r = net->dalloc((size_t)net->max_T * w * 2);
+            *s.stat = (float *)net->dalloc(4 * D * 4);
+            *s.acc = (double *)net->dalloc((2 + 2 * D) * 8);
+            if ((need_r && !*s.r) || !*s.stat || !*s.acc) {
                 set_err("set_bn_train: alloc " + nl.L.name);
                 return -1;
             }
-            bridge_gpu_memset(nl.bnt_stat, 0, 4 * D * 4);
-            bridge_gpu_memset(nl.bnt_acc, 0, (2 + 2 * D) * 8);
+            bridge_gpu_memset(*s.stat, 0, 4 * D * 4);
+            bridge_gpu_memset(*s.acc, 0, (2 + 2 * D) * 8);
         }
+    }
+    if (maxw > net->bnt_w) {  // (grows when the sites changed between two switches: the old pair goes back)
+        net->dfree(net->bnt_ab);
+        net->bnt_w = 0;
         if (!(net->bnt_ab = (float *)net->dalloc((size_t)2 * maxw * 4))) {
             set_err("set_bn_train: alloc backward columns");
             return -1;
@@ -266,16 +376,17 @@ extern "C" int nnet_set_bn_train(KfNet *net, int on) {
 
 extern "C" int nnet_bn_batch_stats(KfNet *net, const char *layer, int which, float *mean, float *var) {
     if (!on_device(net, "bn_batch_stats")) return -1;
-    NetLayer *nl = bnt_layer(net, layer, which, "bn_batch_stats");
+    BntSlot s;
+    NetLayer *nl = bnt_layer(net, layer, which, "bn_batch_stats", s);
     if (!nl) return -1;
-    if (!nl->bnt_act || !nl->bnt_stat) {
+    if (!nl->bnt_act || !*s.stat) {
         set_err(std::string("bn_batch_stats: the last forward did not run ") + layer + " in training mode");
         return -1;
     }
-    const size_t D = (size_t)nl->L.out_dim;
+    const size_t D = (size_t)s.dim;
     // (ordered behind the forward on the current stream, and synchronises; fp32 read = 2x fp16 count)
-    if ((mean && bridge_read_fp16((uint16_t *)mean, nl->bnt_stat, 2 * D)) ||
-        (var && bridge_read_fp16((uint16_t *)var, nl->bnt_stat + D, 2 * D))) {
+    if ((mean && bridge_read_fp16((uint16_t *)mean, *s.stat, 2 * D)) ||
+        (var && bridge_read_fp16((uint16_t *)var, *s.stat + D, 2 * D))) {
         set_err("bn_batch_stats: read");
         return -1;
     }
@@ -283,21 +394,22 @@ extern "C" int nnet_bn_batch_stats(KfNet *net, const char *layer, int which, flo
 }
 
 // (ordered behind the forward on the current stream, and synchronises; a double read = 4x fp16 count)
-static bool bnt_read_acc(NetLayer &nl, std::vector<double> &h) {
-    h.assign(2 + 2 * (size_t)nl.L.out_dim, 0.0);
-    return !nl.bnt_acc || bridge_read_fp16((uint16_t *)h.data(), nl.bnt_acc, h.size() * 4) == 0;
+static bool bnt_read_acc(const BntSlot &s, std::vector<double> &h) {
+    h.assign(2 + 2 * (size_t)s.dim, 0.0);
+    return !*s.acc || bridge_read_fp16((uint16_t *)h.data(), *s.acc, h.size() * 4) == 0;
 }
 
 extern "C" int nnet_bn_stats(KfNet *net, const char *layer, int which, double *count, double *sum, double *sumsq) {
     if (!on_device(net, "bn_stats")) return -1;
-    NetLayer *nl = bnt_layer(net, layer, which, "bn_stats");
+    BntSlot s;
+    NetLayer *nl = bnt_layer(net, layer, which, "bn_stats", s);
     if (!nl) return -1;
     std::vector<double> h;
-    if (!bnt_read_acc(*nl, h)) {
+    if (!bnt_read_acc(s, h)) {
         set_err("bn_stats: read");
         return -1;
     }
-    const size_t D = (size_t)nl->L.out_dim;
+    const size_t D = (size_t)s.dim;
     if (count) *count = h[0];
     if (sum) std::copy(h.begin() + 2, h.begin() + 2 + D, sum);
     if (sumsq) std::copy(h.begin() + 2 + D, h.end(), sumsq);
@@ -306,36 +418,42 @@ extern "C" int nnet_bn_stats(KfNet *net, const char *layer, int which, double *c
 
 extern "C" int nnet_bn_zero_stats(KfNet *net) {
     if (!on_device(net, "bn_zero_stats")) return -1;
-    for (int li : net->bnt_layers) {
-        NetLayer &nl = net->layers[li];
-        if (nl.bnt_acc) bridge_gpu_memset(nl.bnt_acc, 0, (2 + 2 * (size_t)nl.L.out_dim) * 8);
-    }
+    for (int li : net->bnt_layers)
+        for (int which = 0; which < 2; ++which) {
+            BntSlot s;
+            if (bnt_slot(net->layers[li], which, s) && *s.acc) bridge_gpu_memset(*s.acc, 0, (2 + 2 * (size_t)s.dim) * 8);
+        }
     return 0;
 }
 
+// returns the layers committed (a prefinal layer counts once, both of its BatchNorms committed)
 extern "C" int nnet_bn_commit(KfNet *net) {
     if (!on_device(net, "bn_commit")) return -1;
     int n = 0;
     std::vector<double> h;
     for (int li : net->bnt_layers) {
         NetLayer &nl = net->layers[li];
-        if (!nl.bnt_acc) continue;
-        if (!bnt_read_acc(nl, h)) {
-            set_err("bn_commit: read");
-            return -1;
+        bool any = false;
+        for (int which = 0; which < 2; ++which) {
+            BntSlot s;
+            if (!bnt_slot(nl, which, s) || !*s.acc) continue;
+            if (!bnt_read_acc(s, h)) {
+                set_err("bn_commit: read");
+                return -1;
+            }
+            if (!(h[0] > 0.0)) continue;
+            const size_t D = (size_t)s.dim;
+            std::vector<float> mean(D), var(D), gamma(D, 1.f), beta(D, 0.f);
+            for (size_t c = 0; c < D; ++c) {
+                const double mu = h[2 + c] / h[0], v = h[2 + D + c] / h[0] - mu * mu;
+                mean[c] = (float)mu;
+                var[c] = (float)(v > 0.0 ? v : 0.0);
+            }
+            if (nnet_set_bn(net, nl.L.name.c_str(), which, mean.data(), var.data(), gamma.data(), beta.data(), s.eps, s.rms) != 0)
+                return -1;
+            any = true;
         }
-        if (!(h[0] > 0.0)) continue;
-        const size_t D = (size_t)nl.L.out_dim;
-        std::vector<float> mean(D), var(D), gamma(D, 1.f), beta(D, 0.f);
-        for (size_t c = 0; c < D; ++c) {
-            const double mu = h[2 + c] / h[0], v = h[2 + D + c] / h[0] - mu * mu;
-            mean[c] = (float)mu;
-            var[c] = (float)(v > 0.0 ? v : 0.0);
-        }
-        if (nnet_set_bn(net, nl.L.name.c_str(), 0, mean.data(), var.data(), gamma.data(), beta.data(), nl.bn_eps,
-                        nl.bn_rms) != 0)
-            return -1;
-        ++n;
+        n += any;
     }
     return n;
 }

@@ -191,6 +191,9 @@ _sig(nnet, "nnet_spec_augment_rows", _i, _vp, C.c_char_p, _vp, C.POINTER(_i))
 # training-mode BatchNorm (kf_nnet.h nnet_set_bn_train)
 _sig(nnet, "nnet_set_bn_train", _i, _vp, _i)
 _sig(nnet, "nnet_bn_train_layers", _i, _vp, C.POINTER(_i), _i)
+_sig(nnet, "nnet_set_bn_train_sites", _i, _vp, _i)
+_sig(nnet, "nnet_bn_train_sites", _i, _vp)
+_sig(nnet, "nnet_bn_dim", _i, _vp, C.c_char_p, _i)
 _sig(nnet, "nnet_bn_batch_stats", _i, _vp, C.c_char_p, _i, _vp, _vp)
 _sig(nnet, "nnet_bn_stats", _i, _vp, C.c_char_p, _i, C.POINTER(C.c_double), _vp, _vp)
 _sig(nnet, "nnet_bn_zero_stats", _i, _vp)
@@ -772,22 +775,35 @@ class Network:
         the backward, and the count / sum / sumsq accumulators. The frozen statistics are kept."""
         check(nnet.nnet_set_bn_train(self.h, int(on)), "nnet_set_bn_train")
 
+    def set_batchnorm_train_sites(self, sites):
+        """Which kinds of layer set_batchnorm_train governs: an int mask of
+        BN_SITES' values, one of its names, or an iterable / comma-separated string of them:
+        "tdnnf" (the default), "conv", "prefinal", "batchnorm" (the batchnorm-components), "all".
+        Refused while the mode is on."""
+        check(nnet.nnet_set_bn_train_sites(self.h, bn_sites_mask(sites)), "nnet_set_bn_train_sites")
+
+    def batchnorm_train_sites(self) -> int:
+        """The mask set_batchnorm_train_sites set (BN_SITES' values or-ed)."""
+        return nnet.nnet_bn_train_sites(self.h)
+
     def batchnorm_train_layers(self) -> list:
-        """Names of the layers whose BatchNorm the switch governs (today the tdnnf-layers)."""
+        """Names of the layers whose BatchNorm the switch governs under the current sites (the
+        tdnnf-layers by default), in layer order."""
         n = nnet.nnet_bn_train_layers(self.h, None, 0)
         idx = (_i * max(n, 1))()
         nnet.nnet_bn_train_layers(self.h, idx, n)
         return [self.layers[idx[i]][0] for i in range(n)]
 
-    def _bn_dim(self, layer: str) -> int:
-        for name, *_rest, dim in self.layers:
-            if name == layer:
-                return dim
-        raise KfError(f"no layer {layer}")
+    def _bn_dim(self, layer: str, which: int = 0) -> int:
+        d = nnet.nnet_bn_dim(self.h, layer.encode(), int(which))
+        if d < 0:
+            check(-1, "nnet_bn_dim")
+        return d
 
     def batchnorm_batch_stats(self, layer: str, which: int = 0):
-        """(mean, var) float32 [dim] of the last train-mode forward of `layer` (synchronises)."""
-        d = self._bn_dim(layer)
+        """(mean, var) float32 [nnet_bn_dim] of the last train-mode forward of `layer`
+        (synchronises); which = 1: a prefinal-layer's second BatchNorm."""
+        d = self._bn_dim(layer, which)
         mean, var = np.empty(d, np.float32), np.empty(d, np.float32)
         check(nnet.nnet_bn_batch_stats(self.h, layer.encode(), int(which), mean.ctypes.data, var.ctypes.data),
               "nnet_bn_batch_stats")
@@ -795,7 +811,7 @@ class Network:
 
     def batchnorm_stats(self, layer: str, which: int = 0):
         """(count, sum, sumsq): the float64 accumulators of `layer` (synchronises)."""
-        d = self._bn_dim(layer)
+        d = self._bn_dim(layer, which)
         cnt, s, q = C.c_double(), np.empty(d, np.float64), np.empty(d, np.float64)
         check(nnet.nnet_bn_stats(self.h, layer.encode(), int(which), C.byref(cnt), s.ctypes.data, q.ctypes.data),
               "nnet_bn_stats")
@@ -823,6 +839,23 @@ class Network:
         nnet_backward; comm None unbinds."""
         check(nnet.nnet_bind_dp(self.h, comm.h if comm is not None else None, int(bucket_bytes)),
               "nnet_bind_dp")
+
+
+# the sites of training-mode BatchNorm (kf_nnet.h KF_BN_SITE_*)
+BN_SITES = {"tdnnf": 1, "conv": 2, "prefinal": 4, "batchnorm": 8, "all": 15}
+
+
+def bn_sites_mask(sites) -> int:
+    """An int mask, a name of BN_SITES, or several (an iterable or a comma-separated string)."""
+    if isinstance(sites, (int, np.integer)) and not isinstance(sites, bool):
+        return int(sites)
+    names = [t.strip() for t in sites.split(",")] if isinstance(sites, str) else list(sites)
+    mask = 0
+    for n in names:
+        if n not in BN_SITES:
+            raise KfError(f"batchnorm train sites: unknown site {n!r} (one of {', '.join(BN_SITES)})")
+        mask |= BN_SITES[n]
+    return mask
 
 
 def parse_summary(xconfig: str):
@@ -998,6 +1031,8 @@ _sig(core, "kf_row_seg", _i, _vp, _vp, _i, _i, _i, _i)
 _sig(core, "kf_bn_train_stats", _i, _vp, _ll, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig(core, "kf_bn_train_apply", _i, _vp, _ll, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _ll, _f, _vp, _ll)
 _sig(core, "kf_bn_train_bwd_stats", _i, _vp, _ll, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _ll, _vp, _vp, _vp)
+_sig(core, "kf_bn_block_stats", _i, _vp, _ll, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig(core, "kf_bn_block_bwd_stats", _i, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _f, _vp, _vp)
 _sig(core, "kf_bn_train_bwd_apply", _i, _vp, _ll, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _ll, _vp, _vp, _ll,
      _vp, _ll)
 _sig(core, "kf_specaug_rows", _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint64, _ll)

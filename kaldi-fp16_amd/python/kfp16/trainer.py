@@ -21,8 +21,9 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
   1b. (TrainConfig.spec_augment)     -> Network.set_spec_augment: Kaldi's SpecAugment on the
                                      spec-augment-layers, one band and one time mask per eg
   1c. (TrainConfig.batchnorm_train)  -> Network.set_batchnorm_train: Kaldi's training-mode BatchNorm
-                                     on the TDNN-F layers (batch statistics, exact backward, the
-                                     accumulators commit_batchnorm() later freezes)
+                                     on the sites TrainConfig.batchnorm_train_sites names (the
+                                     TDNN-F layers by default; batch statistics, exact backward,
+                                     the accumulators commit_batchnorm() later freezes)
   5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
                                      ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
@@ -90,6 +91,10 @@ class TrainConfig:
     # through them, and the accumulators start from zero (Kaldi's ZeroComponentStats);
     # EgsTrainer.commit_batchnorm() makes them the frozen statistics. False: frozen, as before.
     batchnorm_train: bool = False
+    # batchnorm_train_sites: the layers batchnorm_train governs (Network.set_batchnorm_train_sites,
+    # DESIGN §27): "tdnnf", "conv", "prefinal", "batchnorm", comma-separated, or "all" (what Kaldi
+    # does). With the default nothing more than before is called.
+    batchnorm_train_sites: str = "tdnnf"
     # xent_regularize: Kaldi's --chain.xent-regularize (the recipes use 0.1). > 0: the
     # value goes into the objective's options, Chain.xent writes the output-xent layer's gradient
     # from the numerator posteriors and the backward takes both seeds; result() then also
@@ -198,6 +203,8 @@ class EgsTrainer:
         if self.cfg.spec_augment:
             self.net.set_spec_augment(True, (int(self.cfg.spec_augment_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
         if self.cfg.batchnorm_train:
+            if self.cfg.batchnorm_train_sites != "tdnnf":
+                self.net.set_batchnorm_train_sites(self.cfg.batchnorm_train_sites)
             self.net.set_batchnorm_train(True)
             self.net.batchnorm_zero_stats()
 
