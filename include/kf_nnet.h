@@ -314,10 +314,25 @@ int nnet_spec_augment_rows(KfNet *net, const char *layer, int32_t *host, int *T)
  * `which` is the BatchNorm index of nnet_set_bn (1: prefinal-layer's second one). Composes with
  * dropout, SpecAugment, natural gradient, nnet_update, the orthonormal constraint and
  * nnet_backward_xent. Refused, in either order of the two calls: MXFP8 mode (nnet_set_fp8),
- * implicit dz, row subsampling (the compact row set's scratch row and inexact tail rows are not
- * rows of the layer), a bound data-parallel communicator (the statistics would be each rank's
- * own), and nnet_backward_n. With KF_BN_SITE_COMPONENT, a frame-level batchnorm-component above
- * a trainable layer is refused by nnet_set_bn_train (none of the recipes has one). */
+ * implicit dz, row subsampling under the default row policy (the compact row set's scratch row
+ * and inexact tail rows are not rows of the layer), a bound data-parallel communicator (the
+ * statistics would be each rank's own), and nnet_backward_n. With KF_BN_SITE_COMPONENT, a
+ * frame-level batchnorm-component above a trainable layer is refused by nnet_set_bn_train (none of
+ * the recipes has one).
+ *
+ * nnet_set_bn_train_rows (default KF_BN_ROWS_ALL, the rule above):
+ * KF_BN_ROWS_SUBSAMPLED lets the switch and nnet_set_row_subsampling(3) be on together, in either
+ * order. In a forward that ran on the compact rows (nnet_row_set: tc > 0), a governed BatchNorm of
+ * a compact layer (tdnnf-layers, both BatchNorms of a prefinal-layer, prefinal-xent included) takes
+ * mean and var from the rows c < tc0, the source rows 0 (mod 3), which are exact at every layer;
+ * all tc rows are normalised by them and count grows by tc0. The backward is that forward's exact
+ * derivative: a, b summed over all tc rows and divided by tc0, the correction on the rows c < tc0
+ * only (kf_ops.h kf_bn_train_bwd_stats_rows / _apply_rows). A forward on full rows (row
+ * subsampling off, fp8, a short T) keeps the all-rows rule, and so does every layer below the row
+ * set. A conv-relu-batchnorm-layer directly below the row set that the switch governs
+ * (KF_BN_SITE_CONV) runs on full rows and is gathered, as with KF_RSUB_CONV=0. The policy cannot be
+ * changed while both modes are on; it needs no device (works on a layout-only net).
+ * nnet_bn_train_rows reads it. */
 #define KF_BN_SITE_TDNNF 1
 #define KF_BN_SITE_CONV 2
 #define KF_BN_SITE_PREFINAL 4
@@ -327,6 +342,10 @@ int nnet_set_bn_train(KfNet *net, int on);
 int nnet_set_bn_train_sites(KfNet *net, int sites);
 int nnet_bn_train_sites(const KfNet *net);
 int nnet_bn_train_layers(const KfNet *net, int *idx, int n);
+#define KF_BN_ROWS_ALL 0
+#define KF_BN_ROWS_SUBSAMPLED 1
+int nnet_set_bn_train_rows(KfNet *net, int policy);
+int nnet_bn_train_rows(const KfNet *net);
 int nnet_bn_dim(const KfNet *net, const char *layer, int which);
 int nnet_bn_batch_stats(KfNet *net, const char *layer, int which, float *mean, float *var);
 int nnet_bn_stats(KfNet *net, const char *layer, int which, double *count, double *sum, double *sumsq);

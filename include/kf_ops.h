@@ -499,6 +499,13 @@ int kf_specaug_apply(const void *x, long long ldx, void *y, long long ldy, long 
  *   BatchNormComponent::Backprop; evaluated in double. relu_bit is bit (row ld_mask + c) of the
  *   forward's ReLU mask (ld_mask in bits, a multiple of 8); mask == NULL: a BatchNorm with no ReLU
  *   below it, relu_bit = 1 (ld_mask ignored). dz may not alias g or r.
+ * kf_bn_train_bwd_stats_rows / kf_bn_train_bwd_apply_rows: the backward of
+ *   kf_bn_train_stats over the first stat_rows rows followed by kf_bn_train_apply over all `rows`
+ *   (1 <= stat_rows <= rows, else -1). The sums run over every row, the divisor is n = stat_rows:
+ *   a = sum_{row < rows} dy / n, b = sum_{row < rows} dy yhat / n; then
+ *   dz = rne_fp16(scale (dy - a - yhat b) relu_bit) for row < stat_rows and
+ *   dz = rne_fp16(scale dy relu_bit) from there on (those rows' r is not in the statistics). Same
+ *   shape rules, sums and order; stat_rows == rows is kf_bn_train_bwd_stats / _apply bit for bit.
  *
  * Block statistics: a BatchNorm with block-dim = F on r [rows x H F], where column
  * h F + f belongs to block f (a conv layer: H = height-out, F = num-filters-out) and every sum runs
@@ -521,6 +528,13 @@ int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r, long long
                           const float *scale, const float *shift, float target_rms, const float *a, const float *b,
                           const float *drop, long long ld_drop, const int32_t *row_seg, const uint8_t *mask,
                           long long ld_mask, void *dz, long long lddz);
+int kf_bn_train_bwd_stats_rows(const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows, int D,
+                               const float *scale, const float *shift, float target_rms, const float *drop,
+                               long long ld_drop, const int32_t *row_seg, float *a, float *b);
+int kf_bn_train_bwd_apply_rows(const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows, int D,
+                               const float *scale, const float *shift, float target_rms, const float *a, const float *b,
+                               const float *drop, long long ld_drop, const int32_t *row_seg, const uint8_t *mask,
+                               long long ld_mask, void *dz, long long lddz);
 int kf_bn_block_stats(const void *r, long long ld, int rows, int H, int F, float eps, float target_rms, float *mean,
                       float *var, float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq);
 int kf_bn_block_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int H, int F,

@@ -335,13 +335,22 @@ __global__ __launch_bounds__(kThreads) void k_bn_fwd_apply(const h16 *r, long lo
 // arithmetic and agree bit for bit under an all-ones mask. That rests on the compiler, not on the
 // source, and tests/test_gpu_bn_block.py is what guards it; one explicit rounding order for both
 // variants would change the masked path's bits and is a change of its own.
+//
+// ROWS (kf_bn_train_bwd_apply_rows): the statistics were those of the first stat_rows
+// rows only, so the rows from stat_rows on take dz = rne_fp16(scale dy relu_bit), no correction. The
+// threshold is a property of the row, one branch per row that all but the wave on the threshold
+// takes one way (a first version, selects on r and k0 per element in one fma chain, was bound by
+// its double-precision selects); the columns' constants are still made once for the
+// four rows, and a group of four may straddle stat_rows. ROWS false is the code
+// the kernel always was (stat_rows unused), under the symbol it always had (k_bn_bwd_apply), so
+// kf_bn_train_bwd_apply's bits cannot move; k_bn_bwd_apply_rows is the body with the threshold.
 constexpr int kApplyRows = 4;
-template <bool DROP, bool MASK>
-__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const h16 *g, long long ldg, const h16 *r, long long ldr,
-                                                           int rows, long long units, int d8, const float *scale,
-                                                           const float *shift, double inv_rms, const float *a,
-                                                           const float *b, Drop dr, const uint8_t *mask,
-                                                           long long ld_mask, h16 *dz, long long lddz, unsigned ones) {
+template <bool DROP, bool MASK, bool ROWS>
+__device__ __forceinline__ void bn_bwd_apply_body(const h16 *g, long long ldg, const h16 *r, long long ldr, int rows,
+                                                  int stat_rows, long long units, int d8, const float *scale,
+                                                  const float *shift, double inv_rms, const float *a, const float *b,
+                                                  Drop dr, const uint8_t *mask, long long ld_mask, h16 *dz, long long lddz,
+                                                  unsigned ones) {
     const long long u = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (u >= units) return;
     const long long grp = u / d8;
@@ -370,15 +379,43 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const h16 *g, long lo
         float d[8];
         if constexpr (DROP) load_f8(dr.tab + (long long)dr.row_seg[m] * dr.ld + c0, d);
         half8 o;
+        if (!ROWS || m < stat_rows) {  // (per row: the same for its 8 columns and for every lane on the row)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            double dy = (double)h2f(gv[e]);
-            if constexpr (DROP) dy *= (double)d[e];
-            const double w = fma(scd[e], dy, -fma(k1[e], (double)h2f(rv[e]), k0[e]));
-            o[e] = ((bits >> e) & 1u) ? f2h((float)w) : (h16)0.f;
+            for (int e = 0; e < 8; ++e) {
+                double dy = (double)h2f(gv[e]);
+                if constexpr (DROP) dy *= (double)d[e];
+                const double w = fma(scd[e], dy, -fma(k1[e], (double)h2f(rv[e]), k0[e]));
+                o[e] = ((bits >> e) & 1u) ? f2h((float)w) : (h16)0.f;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                double dy = (double)h2f(gv[e]);
+                if constexpr (DROP) dy *= (double)d[e];
+                o[e] = ((bits >> e) & 1u) ? f2h((float)(scd[e] * dy)) : (h16)0.f;
+            }
         }
         store_h8(dz + m * lddz + c0, o);
     }
+}
+template <bool DROP, bool MASK>
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const h16 *g, long long ldg, const h16 *r, long long ldr,
+                                                           int rows, long long units, int d8, const float *scale,
+                                                           const float *shift, double inv_rms, const float *a,
+                                                           const float *b, Drop dr, const uint8_t *mask,
+                                                           long long ld_mask, h16 *dz, long long lddz, unsigned ones) {
+    bn_bwd_apply_body<DROP, MASK, false>(g, ldg, r, ldr, rows, rows, units, d8, scale, shift, inv_rms, a, b, dr, mask, ld_mask,
+                                         dz, lddz, ones);
+}
+template <bool DROP, bool MASK>
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply_rows(const h16 *g, long long ldg, const h16 *r, long long ldr,
+                                                                int rows, int stat_rows, long long units, int d8,
+                                                                const float *scale, const float *shift, double inv_rms,
+                                                                const float *a, const float *b, Drop dr,
+                                                                const uint8_t *mask, long long ld_mask, h16 *dz,
+                                                                long long lddz, unsigned ones) {
+    bn_bwd_apply_body<DROP, MASK, true>(g, ldg, r, ldr, rows, stat_rows, units, d8, scale, shift, inv_rms, a, b, dr, mask,
+                                        ld_mask, dz, lddz, ones);
 }
 
 bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -457,16 +494,21 @@ extern "C" int kf_bn_train_apply(const void *r, long long ld, int rows, int D, c
     return launched(what) ? 0 : -1;
 }
 
-extern "C" int kf_bn_train_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
-                                     const float *scale, const float *shift, float target_rms, const float *drop,
-                                     long long ld_drop, const int32_t *row_seg, float *a, float *b) {
-    kf_take_pending(__func__);
-    const char *what = "kf_bn_train_bwd_stats";
+namespace {
+
+// kf_bn_train_bwd_stats / _rows: the sums over `rows`, the divisor stat_rows
+int bwd_stats(const char *what, const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows, int D,
+              const float *scale, const float *shift, float target_rms, const float *drop, long long ld_drop,
+              const int32_t *row_seg, float *a, float *b) {
     if (!shape_ok(what, rows, D) || !tensor_ok(what, "g", g, ldg, D) || !tensor_ok(what, "r", r, ldr, D) ||
         !drop_ok(what, drop, ld_drop, row_seg, D))
         return -1;
     if (!scale || !shift || !a || !b || !(target_rms > 0.f)) {
         kf_report_error("%s: needs scale, shift, a, b and target_rms > 0", what);
+        return -1;
+    }
+    if (stat_rows < 1 || stat_rows > rows) {
+        kf_report_error("%s: needs 1 <= stat_rows <= rows (stat_rows=%d rows=%d)", what, stat_rows, rows);
         return -1;
     }
     double *part = partials(what, rows, D);
@@ -477,16 +519,15 @@ extern "C" int kf_bn_train_bwd_stats(const void *g, long long ldg, const void *r
     if (drop) k_bn_bwd_part<true><<<grid, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, D, dr, part);
     else k_bn_bwd_part<false><<<grid, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, D, dr, part);
     k_bn_bwd_finish<kFinCols><<<(unsigned)((D + kFinCols - 1) / kFinCols), kThreads, 0, kf_stream()>>>(
-        part, nchunk, (double)rows, D, scale, shift, 1.0 / (double)target_rms, a, b);
+        part, nchunk, (double)stat_rows, D, scale, shift, 1.0 / (double)target_rms, a, b);
     return launched(what) ? 0 : -1;
 }
 
-extern "C" int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
-                                     const float *scale, const float *shift, float target_rms, const float *a,
-                                     const float *b, const float *drop, long long ld_drop, const int32_t *row_seg,
-                                     const uint8_t *mask, long long ld_mask, void *dz, long long lddz) {
-    kf_take_pending(__func__);
-    const char *what = "kf_bn_train_bwd_apply";
+// kf_bn_train_bwd_apply / _rows. stat_rows == rows launches the kernel without the row threshold,
+// the one kf_bn_train_bwd_apply always launched.
+int bwd_apply(const char *what, const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows, int D,
+              const float *scale, const float *shift, float target_rms, const float *a, const float *b, const float *drop,
+              long long ld_drop, const int32_t *row_seg, const uint8_t *mask, long long ld_mask, void *dz, long long lddz) {
     if (!shape_ok(what, rows, D) || !tensor_ok(what, "g", g, ldg, D) || !tensor_ok(what, "r", r, ldr, D) ||
         !tensor_ok(what, "dz", dz, lddz, D) || !cols_ok(what, "scale", scale) || !cols_ok(what, "shift", shift) ||
         !cols_ok(what, "a", a) || !cols_ok(what, "b", b) || !drop_ok(what, drop, ld_drop, row_seg, D))
@@ -495,20 +536,67 @@ extern "C" int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r
         kf_report_error("%s: needs the ReLU mask with ld_mask >= D bits, ld_mask %% 8 == 0 (or none), and target_rms > 0", what);
         return -1;
     }
+    if (stat_rows < 1 || stat_rows > rows) {
+        kf_report_error("%s: needs 1 <= stat_rows <= rows (stat_rows=%d rows=%d)", what, stat_rows, rows);
+        return -1;
+    }
     const int d8 = D / 8;
     const long long units = (long long)((rows + kApplyRows - 1) / kApplyRows) * d8;
     const unsigned nblk = (unsigned)((units + kThreads - 1) / kThreads);
     const Drop dr{drop, ld_drop, row_seg};
     const double inv_rms = 1.0 / (double)target_rms;
-#define KF_BN_BWD_APPLY(DROP, MASK)                                                                                    \
-    k_bn_bwd_apply<DROP, MASK><<<nblk, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, units, d8, \
-                                                                   scale, shift, inv_rms, a, b, dr, mask, ld_mask, (h16 *)dz, lddz, 0xFFu)
-    if (drop && mask) KF_BN_BWD_APPLY(true, true);
-    else if (mask) KF_BN_BWD_APPLY(false, true);
-    else if (drop) KF_BN_BWD_APPLY(true, false);
-    else KF_BN_BWD_APPLY(false, false);
+#define KF_BN_BWD_APPLY(KERNEL, ...)                                                                                   \
+    KERNEL<<<nblk, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, rows, __VA_ARGS__ units, d8, scale, \
+                                               shift, inv_rms, a, b, dr, mask, ld_mask, (h16 *)dz, lddz, 0xFFu)
+    if (stat_rows < rows) {
+        if (drop && mask) KF_BN_BWD_APPLY((k_bn_bwd_apply_rows<true, true>), stat_rows, );
+        else if (mask) KF_BN_BWD_APPLY((k_bn_bwd_apply_rows<false, true>), stat_rows, );
+        else if (drop) KF_BN_BWD_APPLY((k_bn_bwd_apply_rows<true, false>), stat_rows, );
+        else KF_BN_BWD_APPLY((k_bn_bwd_apply_rows<false, false>), stat_rows, );
+    } else {
+        if (drop && mask) KF_BN_BWD_APPLY((k_bn_bwd_apply<true, true>), );
+        else if (mask) KF_BN_BWD_APPLY((k_bn_bwd_apply<false, true>), );
+        else if (drop) KF_BN_BWD_APPLY((k_bn_bwd_apply<true, false>), );
+        else KF_BN_BWD_APPLY((k_bn_bwd_apply<false, false>), );
+    }
 #undef KF_BN_BWD_APPLY
     return launched(what) ? 0 : -1;
+}
+
+}  // namespace
+
+extern "C" int kf_bn_train_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                                     const float *scale, const float *shift, float target_rms, const float *drop,
+                                     long long ld_drop, const int32_t *row_seg, float *a, float *b) {
+    kf_take_pending(__func__);
+    return bwd_stats("kf_bn_train_bwd_stats", g, ldg, r, ldr, rows, rows, D, scale, shift, target_rms, drop, ld_drop, row_seg, a,
+                     b);
+}
+
+extern "C" int kf_bn_train_bwd_stats_rows(const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows,
+                                          int D, const float *scale, const float *shift, float target_rms, const float *drop,
+                                          long long ld_drop, const int32_t *row_seg, float *a, float *b) {
+    kf_take_pending(__func__);
+    return bwd_stats("kf_bn_train_bwd_stats_rows", g, ldg, r, ldr, rows, stat_rows, D, scale, shift, target_rms, drop, ld_drop,
+                     row_seg, a, b);
+}
+
+extern "C" int kf_bn_train_bwd_apply(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                                     const float *scale, const float *shift, float target_rms, const float *a,
+                                     const float *b, const float *drop, long long ld_drop, const int32_t *row_seg,
+                                     const uint8_t *mask, long long ld_mask, void *dz, long long lddz) {
+    kf_take_pending(__func__);
+    return bwd_apply("kf_bn_train_bwd_apply", g, ldg, r, ldr, rows, rows, D, scale, shift, target_rms, a, b, drop, ld_drop,
+                     row_seg, mask, ld_mask, dz, lddz);
+}
+
+extern "C" int kf_bn_train_bwd_apply_rows(const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows,
+                                          int D, const float *scale, const float *shift, float target_rms, const float *a,
+                                          const float *b, const float *drop, long long ld_drop, const int32_t *row_seg,
+                                          const uint8_t *mask, long long ld_mask, void *dz, long long lddz) {
+    kf_take_pending(__func__);
+    return bwd_apply("kf_bn_train_bwd_apply_rows", g, ldg, r, ldr, rows, stat_rows, D, scale, shift, target_rms, a, b, drop,
+                     ld_drop, row_seg, mask, ld_mask, dz, lddz);
 }
 
 // ---- block statistics: the entries ----

@@ -311,8 +311,9 @@ struct BackwardPass {
     bool linear(Step &s), attention(Step &s), prefinal(Step &s), combine(Step &s), tdnnf(Step &s), conv(Step &s);
     KfOperand masked(const Step &s, const Tdnnf &t, KfOperand o) const;
     bool bn_train_dz(Step &s, int ib);
-    bool bn_site_dz(const void *g, const void *r, int rows, int H, int F, const float *stat, float rms, const uint8_t *mask,
-                    void *dz_out, const std::string &what);
+    bool bn_rows_entries();
+    bool bn_site_dz(const void *g, const void *r, int rows, int stat_rows, int H, int F, const float *stat, float rms,
+                    const uint8_t *mask, void *dz_out, const std::string &what);
     void *bn_site_slot(const NetLayer &nl);
     bool tdnnf_affine_wgrad(Step &s, const Tdnnf &t), tdnnf_affine_dgrad(Step &s, const Tdnnf &t);
     bool tdnnf_affine_dgrad_mx(Step &s, const Tdnnf &t, const KfEpilogue &E1, void *edge);
@@ -474,7 +475,7 @@ int BackwardPass::step(int li, int ndone) {
     const bool first_c = net->rs.Tc && li == net->first_c;
     Step s{nl, li, rows_of(net, li), net->T,
            // (the first compact layer read its input gathered to the compact rows)
-           first_c && !net->conv_c ? net->xc : act_of(net, nl.input), nl.needs_dx && nl.input >= 0, first_c,
+           first_c && !conv_c_on(net) ? net->xc : act_of(net, nl.input), nl.needs_dx && nl.input >= 0, first_c,
            // (the xent branch's last step: its input gradient goes to gx, not into the ring)
            branch && li == branch->back() ? net->gx : net->dz[flip], net->g[flip],
            // (this step's dbott buffer was last written at step i - 3 or earlier)
@@ -575,7 +576,7 @@ bool BackwardPass::to_full_epilogue(Step &s) {
         set_err("row subsampling: unsupported input gradient into " + pl.L.name);
         return false;
     }
-    if (E.mask_in && !net->conv_c) {  // (a compact conv's mask already is in compact rows)
+    if (E.mask_in && !conv_c_on(net)) {  // (a compact conv's mask already is in compact rows)
         if (!ck(kf_gather_rows(net->mc, pl.mask, w / 8, s.Tfull, net->rs.Tc0, net->rs.Tc), "row set mask gather")) return false;
         E.mask_in = net->mc;
     }
@@ -583,9 +584,14 @@ bool BackwardPass::to_full_epilogue(Step &s) {
     return true;
 }
 bool BackwardPass::to_full_scatter(Step &s) {
-    const int w = net->layers[s.nl.input].L.out_dim;
-    if (!net->conv_c)
-        return ck(kf_scatter_rows(s.dz_next, net->dzc, (long long)w * 2, s.Tfull, net->rs.Tc0, net->rs.Tc), "row set scatter");
+    const NetLayer &pl = net->layers[s.nl.input];
+    const int w = pl.L.out_dim;
+    // (a conv under training-mode BatchNorm took the raw g, dx_epilogue: it belongs in the g slot,
+    // where BackwardPass::conv's bn_site_dz reads it and writes dz into the slot left unwritten)
+    if (!conv_c_on(net))
+        return ck(kf_scatter_rows(pl.bnt_act ? s.g_next : s.dz_next, net->dzc, (long long)w * 2, s.Tfull, net->rs.Tc0,
+                                  net->rs.Tc),
+                  "row set scatter");
     // the conv below reads the compact rows (net->dzc); only its tail window (full rows
     // from window_t0, conv_window) takes the scattered form
     const int r0 = net->rs.window_t0;
@@ -638,7 +644,7 @@ bool BackwardPass::prefinal(Step &s) {
     const bool bnt = nl.bnt_act;
     if (bnt && nl.has_bn2) {
         void *slot = bn_site_slot(nl);
-        if (!slot || !bn_site_dz(gcur, nl.bnt_r2, T, 1, small, nl.bnt_stat2, nl.bn2_rms, nullptr, slot,
+        if (!slot || !bn_site_dz(gcur, nl.bnt_r2, T, bnt_stat_rows(net, s.li), 1, small, nl.bnt_stat2, nl.bn2_rms, nullptr, slot,
                                  "prefinal " + nl.L.name + " (small)"))
             return false;
     }
@@ -670,7 +676,8 @@ bool BackwardPass::prefinal(Step &s) {
     KfOperand A1 = op_base(dz, small, T, small, 1);
     KfOperand B1 = op_base(wptr(net, nl.pW2), small, big, small, 1);
     if (!ck(kf_gemm_fused(T, big, small, &A1, &B1, &E1), "prefinal small dgrad")) return false;
-    if (bnt && !bn_site_dz(gbig, nl.bnt_r, T, 1, big, nl.bnt_stat, nl.bn_rms, nl.mask, dzbig, "prefinal " + nl.L.name + " (big)"))
+    if (bnt && !bn_site_dz(gbig, nl.bnt_r, T, bnt_stat_rows(net, s.li), 1, big, nl.bnt_stat, nl.bn_rms, nl.mask, dzbig,
+                           "prefinal " + nl.L.name + " (big)"))
         return false;
     KfOperand A3 = op_base(s.x, din, T, din, 0);
     KfOperand B3 = op_base(dzbig, big, T, big, 0);
@@ -706,7 +713,7 @@ bool BackwardPass::combine(Step &s) {
             if (q.L.type == LayerType::Batchnorm && q.bnt_act) {
                 // training-mode BatchNorm over the B rows: its dz into the layer's own
                 // buffer (the apply may not write over g)
-                if (!bn_site_dz(gq, act_of(net, q.input), rowsB, 1, qd, q.bnt_stat, q.bn_rms, nullptr, q.bnt_r,
+                if (!bn_site_dz(gq, act_of(net, q.input), rowsB, rowsB, 1, qd, q.bnt_stat, q.bn_rms, nullptr, q.bnt_r,
                                 "batchnorm-component " + q.L.name))
                     return false;
                 gq = q.bnt_r;
@@ -786,18 +793,36 @@ bool BackwardPass::bn_train_dz(Step &s, int ib) {
     const float *drop = nl.drop_act ? nl.drop : nullptr;
     const int32_t *rseg = drop ? drop_rows(net, nl.compact) : nullptr;
     float *a = net->bnt_ab, *b = net->bnt_ab + net->bnt_w;
+    // compact rows: the statistics were those of the rows c < Tc0, so the sums run over
+    // all Tc rows with the divisor Tc0 and only those rows take the correction
+    const int Ts = bnt_stat_rows(net, s.li);
+    if (Ts < T) {
+        if (!bn_rows_entries()) return false;
+        return ck(kf_bn_train_bwd_stats_rows(gcur, D, nl.bnt_r, D, T, Ts, D, sc, sh, nl.bn_rms, drop, D, rseg, a, b),
+                  "tdnnf batchnorm backward statistics") &&
+               ck(kf_bn_train_bwd_apply_rows(gcur, D, nl.bnt_r, D, T, Ts, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
+                                             net->dz[ib], D),
+                  "tdnnf batchnorm backward apply");
+    }
     return ck(kf_bn_train_bwd_stats(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, drop, D, rseg, a, b),
               "tdnnf batchnorm backward statistics") &&
            ck(kf_bn_train_bwd_apply(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
                                     net->dz[ib], D),
               "tdnnf batchnorm backward apply");
 }
+// the _rows entries a backward on compact rows needs (weak references, net_internal.h)
+bool BackwardPass::bn_rows_entries() {
+    if (kf_bn_train_bwd_stats_rows && kf_bn_train_bwd_apply_rows) return true;
+    set_err("backward: this build of libkaldi_fp16 has no training-mode BatchNorm kernels for the row-subsampled step");
+    return false;
+}
 
 // Training-mode BatchNorm backward of a conv, prefinal or batchnorm-component site:
 // a, b over g and r [rows x H F] (block f = column h F + f), then dz = scale (g - a - yhat b)
 // relu_bit through the dense [rows H x F] view, on the chain stream. mask NULL: no ReLU below the
-// BatchNorm. One a | b pair serves every site: the chain stream runs them in order.
-bool BackwardPass::bn_site_dz(const void *g, const void *r, int rows, int H, int F, const float *stat, float rms,
+// BatchNorm. One a | b pair serves every site: the chain stream runs them in order. stat_rows < rows:
+// the statistics were those of the first stat_rows rows (the _rows entries).
+bool BackwardPass::bn_site_dz(const void *g, const void *r, int rows, int stat_rows, int H, int F, const float *stat, float rms,
                               const uint8_t *mask, void *dz_out, const std::string &what) {
     if (!g || !r || !stat || !dz_out || g == dz_out || F > net->bnt_w || !kf_bn_train_bwd_stats || !kf_bn_train_bwd_apply ||
         (H > 1 && !kf_bn_block_bwd_stats)) {
@@ -806,6 +831,15 @@ bool BackwardPass::bn_site_dz(const void *g, const void *r, int rows, int H, int
     }
     const float *sc = stat + 2 * F, *sh = stat + 3 * F;
     float *a = net->bnt_ab, *b = net->bnt_ab + net->bnt_w;
+    if (stat_rows < rows) {  // a prefinal layer on compact rows (H = 1: no conv is compact under the mode)
+        if (H != 1) set_err("backward: training-mode BatchNorm of " + what + " has block statistics on a row subset");
+        if (H != 1 || !bn_rows_entries()) return false;
+        return ck(kf_bn_train_bwd_stats_rows(g, F, r, F, rows, stat_rows, F, sc, sh, rms, nullptr, 0, nullptr, a, b),
+                  (what + " batchnorm backward statistics").c_str()) &&
+               ck(kf_bn_train_bwd_apply_rows(g, F, r, F, rows, stat_rows, F, sc, sh, rms, a, b, nullptr, 0, nullptr, mask, F,
+                                             dz_out, F),
+                  (what + " batchnorm backward apply").c_str());
+    }
     const int rc = H == 1 ? kf_bn_train_bwd_stats(g, F, r, F, rows, F, sc, sh, rms, nullptr, 0, nullptr, a, b)
                           : kf_bn_block_bwd_stats(g, (long long)H * F, r, (long long)H * F, rows, H, F, sc, sh, rms, a, b);
     return ck(rc, (what + " batchnorm backward statistics").c_str()) &&
@@ -961,7 +995,7 @@ bool BackwardPass::conv(Step &s) {
     // rows x height-out, then dz into the ring slot, before anything below reads dz
     if (nl.bnt_act) {
         void *slot = bn_site_slot(nl);
-        if (!slot || !bn_site_dz(gcur, nl.bnt_r, s.T, L.hout, L.fout, nl.bnt_stat, nl.bn_rms, nl.mask, slot, "conv " + L.name))
+        if (!slot || !bn_site_dz(gcur, nl.bnt_r, s.T, s.T, L.hout, L.fout, nl.bnt_stat, nl.bn_rms, nl.mask, slot, "conv " + L.name))
             return false;
     }
     // compact-row conv: the tail window runs first, on the weight-gradient stream beside

@@ -52,19 +52,21 @@ KfEpilogue epi_relu_bn(KfNet *net, NetLayer &nl, int pb, long long ldo) {
 // Training-mode BatchNorm of a governed site: the batch statistics of r [rows x H F]
 // (block f = column h F + f; H = 1: the column entries), then r scale + shift into out through the
 // dense [rows H x F] view. stat = mean | var | scale | shift, acc = count (2) | sum | sumsq.
-bool bnt_normalise(const void *r, int rows, int H, int F, float eps, float rms, float *stat, double *acc, void *out,
-                   const std::string &what) {
+// The statistics run over the first stat_rows rows, the apply over all `rows` (a
+// compact layer's rows c < Tc0 against its Tc; everywhere else the two are equal).
+bool bnt_normalise(const void *r, int stat_rows, int rows, int H, int F, float eps, float rms, float *stat, double *acc,
+                   void *out, const std::string &what) {
     // (H = 1, a prefinal layer or a batchnorm-component: wide rows, the column entry's lane map)
-    const int rc = H == 1 ? kf_bn_train_stats(r, F, rows, F, eps, rms, stat, stat + F, stat + 2 * F, stat + 3 * F, acc, acc + 2,
-                                              acc + 2 + F)
-                          : kf_bn_block_stats(r, (long long)H * F, rows, H, F, eps, rms, stat, stat + F, stat + 2 * F,
+    const int rc = H == 1 ? kf_bn_train_stats(r, F, stat_rows, F, eps, rms, stat, stat + F, stat + 2 * F, stat + 3 * F, acc,
+                                              acc + 2, acc + 2 + F)
+                          : kf_bn_block_stats(r, (long long)H * F, stat_rows, H, F, eps, rms, stat, stat + F, stat + 2 * F,
                                               stat + 3 * F, acc, acc + 2, acc + 2 + F);
     return ck(rc, (what + " batchnorm statistics").c_str()) &&
            ck(kf_bn_train_apply(r, F, rows * H, F, stat + 2 * F, stat + 3 * F, nullptr, 0, nullptr, nullptr, 0, 0.f, out, F),
               (what + " batchnorm apply").c_str());
 }
 bool bnt_conv(NetLayer &nl, int T) {
-    return bnt_normalise(nl.bnt_r, T, nl.L.hout, nl.L.fout, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.act, "conv");
+    return bnt_normalise(nl.bnt_r, T, T, nl.L.hout, nl.L.fout, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.act, "conv");
 }
 // the epilogue of a governed conv / prefinal affine: r and the ReLU mask, no scale or shift
 KfEpilogue epi_relu_r(KfNet *net, NetLayer &nl, int pb, long long ldo) {
@@ -155,7 +157,9 @@ bool fwd_conv(KfNet *net, int li, const void *x, int T) {
     KfEpilogue E = epi_relu_bn(net, nl, nl.pb, L.fout);
     if (net->fp8 && nl.a8.q) set_out8(E, nl.a8), E.ldo8 = L.fout;  // rows (t,h) of fout: the [t x hout*fout] copy
     if (conv_compact(net, li)) return fwd_conv_compact(net, nl, K, A, B, E);
-    if (nl.bnt_act) {  // (row subsampling and MXFP8 are refused with the mode: full rows, no out8)
+    // (MXFP8 is refused with the mode and a governed conv below the row set runs on full rows,
+    // conv_c_on: no out8, no compact rows)
+    if (nl.bnt_act) {
         KfEpilogue Er = epi_relu_r(net, nl, nl.pb, L.fout);
         return ck(kf_gemm_fused(T * L.hout, L.fout, K, &A, &B, &Er), "conv") && bnt_conv(nl, T);
     }
@@ -219,14 +223,15 @@ bool fwd_tdnnf(KfNet *net, int li, const void *x) {
     }
     if (!nl.bnt_act) return ck(kf_gemm_fused(T, dout, f8b ? nl.w8b.ld : kaff, &A2, &B2, &E2), "tdnnf affine");
     // training-mode BatchNorm: the GEMM writes r = relu(affine + bias) and the mask
-    // only; the batch statistics of r, then the epilogue's scale / shift / dropout / bypass on them
+    // only; the batch statistics of r, then the epilogue's scale / shift / dropout / bypass on them.
+    // On compact rows the statistics are those of the rows c < Tc0, applied to all Tc.
     KfEpilogue Er = epi_relu_bn(net, nl, nl.pb2, dout);
     Er.out = nl.bnt_r;
     Er.scale = Er.shift = nullptr;
     float *const st = nl.bnt_stat;
     return ck(kf_gemm_fused(T, dout, kaff, &A2, &B2, &Er), "tdnnf affine") &&
-           ck(kf_bn_train_stats(nl.bnt_r, dout, T, dout, nl.bn_eps, nl.bn_rms, st, st + dout, st + 2 * dout, st + 3 * dout,
-                                nl.bnt_acc, nl.bnt_acc + 2, nl.bnt_acc + 2 + dout),
+           ck(kf_bn_train_stats(nl.bnt_r, dout, bnt_stat_rows(net, li), dout, nl.bn_eps, nl.bn_rms, st, st + dout, st + 2 * dout,
+                                st + 3 * dout, nl.bnt_acc, nl.bnt_acc + 2, nl.bnt_acc + 2 + dout),
               "tdnnf batchnorm statistics") &&
            ck(kf_bn_train_apply(nl.bnt_r, dout, T, dout, st + 2 * dout, st + 3 * dout, E2.drop, E2.ld_drop, E2.row_seg,
                                 E2.resid, E2.ldr, E2.resid_alpha, nl.act, dout),
@@ -291,11 +296,12 @@ bool fwd_prefinal(KfNet *net, int li, const void *x) {
         KfEpilogue E2 = epi0();
         E2.out = nl.has_bn2 ? nl.bnt_r2 : nl.act;
         E2.ldo = small;
+        const int Ts = bnt_stat_rows(net, li);
         return ck(kf_gemm_fused(T, big, din, &A, &B, &Er), "prefinal big") &&
-               bnt_normalise(nl.bnt_r, T, 1, big, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.aux, "prefinal big") &&
+               bnt_normalise(nl.bnt_r, Ts, T, 1, big, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.aux, "prefinal big") &&
                ck(kf_gemm_fused(T, small, big, &A2, &B2, &E2), "prefinal small") &&
-               (!nl.has_bn2 || bnt_normalise(nl.bnt_r2, T, 1, small, nl.bn2_eps, nl.bn2_rms, nl.bnt_stat2, nl.bnt_acc2, nl.act,
-                                             "prefinal small"));
+               (!nl.has_bn2 || bnt_normalise(nl.bnt_r2, Ts, T, 1, small, nl.bn2_eps, nl.bn2_rms, nl.bnt_stat2, nl.bnt_acc2,
+                                             nl.act, "prefinal small"));
     }
     KfEpilogue E = epi_relu_bn(net, nl, nl.pb, big);
     E.out = nl.aux;
@@ -323,8 +329,8 @@ bool fwd_layer(KfNet *net, int li, const void *x, int T) {
             return ck(kf_small_gemm(x, L.in_dim, nl.idct, nl.act, L.out_dim, T, L.in_dim, L.out_dim), "idct");
         case LayerType::Batchnorm:
             if (nl.bnt_act)  // (the statistics of the input itself; a per-sequence layer's rows are the sequences)
-                return bnt_normalise(x, nl.per_seq ? net->B : T, 1, L.out_dim, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc,
-                                     nl.act, "batchnorm");
+                return bnt_normalise(x, nl.per_seq ? net->B : T, nl.per_seq ? net->B : T, 1, L.out_dim, nl.bn_eps, nl.bn_rms,
+                                     nl.bnt_stat, nl.bnt_acc, nl.act, "batchnorm");
             return ck(kf_bn_apply(x, nl.act, nl.per_seq ? net->B : T, L.out_dim, nl.bn_scale, nl.bn_shift), "batchnorm");
         case LayerType::SpecAugment:
             // inactive: the alias of its input (forward.go:225-231 passes through). Active: the
@@ -487,7 +493,7 @@ int forward_impl(KfNet *net, const void *features, int T) {
     for (size_t li = 0; li < net->layers.size(); ++li) {
         NetLayer &nl = net->layers[li];
         const void *x = act_of(net, nl.input);
-        if (net->rs.Tc && (int)li == net->first_c && !net->conv_c) {  // the conv stack's output on the compact rows
+        if (net->rs.Tc && (int)li == net->first_c && !conv_c_on(net)) {  // the conv stack's output on the compact rows
             if (!ck(kf_gather_rows(net->xc, x, (long long)nl.L.in_dim * 2, T, net->rs.Tc0, net->rs.Tc), "row set gather"))
                 return -1;
             x = net->xc;

@@ -52,7 +52,11 @@ struct Conflict {
     Mode a, b;
     const char *reason;                   // follows the phrase after ": ", or NULL
     std::string (*where)(const KfNet *);  // or: the pair conflicts only where this says why ("": nowhere)
+    bool (*lifted)(const KfNet *) = nullptr;  // or: the pair combines while this holds (the text is the plain one otherwise)
 };
+// nnet_set_bn_train_rows(KF_BN_ROWS_SUBSAMPLED), DESIGN §28: the statistics of a compact layer run
+// over the rows c < Tc0, which are rows of the layer
+bool bn_rows_subsampled(const KfNet *net) { return net->bnt_rows == KF_BN_ROWS_SUBSAMPLED; }
 // (implicit dz x natural gradient is not here: BackwardPass::begin refuses it, no setter does)
 const Conflict kConflicts[] = {
     {Mode::Fp8, Mode::NaturalGradient, nullptr, nullptr},
@@ -62,7 +66,7 @@ const Conflict kConflicts[] = {
     {Mode::ImplicitDz, Mode::Dropout, nullptr, nullptr},
     {Mode::ImplicitDz, Mode::BnTrain, nullptr, nullptr},
     // (the compact row set's scratch row and inexact tail rows are not rows of the layer)
-    {Mode::RowSubsampling, Mode::BnTrain, nullptr, nullptr},
+    {Mode::RowSubsampling, Mode::BnTrain, nullptr, nullptr, bn_rows_subsampled},
     {Mode::NaturalGradient, Mode::DataParallel, nullptr, nullptr},
     {Mode::DataParallel, Mode::BnTrain, "the statistics would be each rank's own", nullptr},
     {Mode::BackwardN, Mode::NaturalGradient, nullptr, nullptr},
@@ -79,7 +83,7 @@ bool admit(KfNet *net, Mode turning_on, const char *fn) {
     for (const Conflict &c : kConflicts) {
         if (c.a != turning_on && c.b != turning_on) continue;
         const Mode other = c.a == turning_on ? c.b : c.a;
-        if (!mode_on(net, other)) continue;
+        if (!mode_on(net, other) || (c.lifted && c.lifted(net))) continue;
         if (c.where) {
             const std::string why = c.where(net);
             if (why.empty()) continue;
@@ -180,6 +184,24 @@ extern "C" int nnet_set_row_subsampling(KfNet *net, int stride) {
     net->rs_nt = nt;
     net->maxTc = maxTc;
     net->rsub = 3;
+    return 0;
+}
+
+extern "C" int nnet_bn_train_rows(const KfNet *net) { return net ? net->bnt_rows : -1; }
+
+// (no device needed: the policy is a number the switches and the passes read)
+extern "C" int nnet_set_bn_train_rows(KfNet *net, int policy) {
+    if (!net) return -1;
+    if (policy != KF_BN_ROWS_ALL && policy != KF_BN_ROWS_SUBSAMPLED) {
+        set_err("set_bn_train_rows: policy=" + std::to_string(policy) + " is not KF_BN_ROWS_ALL or KF_BN_ROWS_SUBSAMPLED");
+        return -1;
+    }
+    if (policy != net->bnt_rows && mode_on(net, Mode::RowSubsampling) && mode_on(net, Mode::BnTrain)) {
+        set_err("set_bn_train_rows: not supported with row subsampling (nnet_set_row_subsampling) and training-mode "
+                "BatchNorm (nnet_set_bn_train) both on: switch one of them off first");
+        return -1;
+    }
+    net->bnt_rows = policy;
     return 0;
 }
 

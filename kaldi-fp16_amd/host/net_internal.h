@@ -43,6 +43,8 @@ KF_HIDDEN void set_err(const std::string &s);
 #pragma weak kf_bn_train_apply
 #pragma weak kf_bn_train_bwd_stats
 #pragma weak kf_bn_train_bwd_apply
+#pragma weak kf_bn_train_bwd_stats_rows
+#pragma weak kf_bn_train_bwd_apply_rows
 #pragma weak kf_bn_block_stats
 #pragma weak kf_bn_block_bwd_stats
 
@@ -320,6 +322,10 @@ struct KfNet {
     int bnt_on = 0;
     float *bnt_ab = nullptr;
     int bnt_w = 0;
+    // nnet_set_bn_train_rows: KF_BN_ROWS_SUBSAMPLED lets the switch and row subsampling
+    // be on together; a governed BatchNorm of a compact layer then takes its statistics from the
+    // rows c < Tc0 of a compact forward (bnt_stat_rows below)
+    int bnt_rows = 0;  // KF_BN_ROWS_ALL
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]
@@ -507,9 +513,21 @@ inline const int32_t *drop_rows(const KfNet *net, bool compact) {
 inline int rows_of(const KfNet *net, int idx) {
     return (idx >= 0 && net->rs.Tc > 0 && net->layers[idx].compact) ? net->rs.Tc : net->T;
 }
+// The conv below the compact layers under training-mode BatchNorm (KF_BN_SITE_CONV):
+// its statistics run over all rows like every other conv's, so it runs on full rows and the first
+// compact layer reads it gathered (the path KF_RSUB_CONV=0 selects). bnt_act is the current
+// forward's, set before its first layer runs.
+inline bool conv_c_on(const KfNet *net) {
+    return net->conv_c && net->first_c >= 0 && !net->layers[net->layers[net->first_c].input].bnt_act;
+}
 // the conv below the compact layers, evaluated on the compact rows (KfNet.conv_c)
 inline bool conv_compact(const KfNet *net, int idx) {
-    return net->rs.Tc > 0 && net->conv_c && net->first_c >= 0 && idx >= 0 && idx == net->layers[net->first_c].input;
+    return net->rs.Tc > 0 && conv_c_on(net) && idx >= 0 && idx == net->layers[net->first_c].input;
+}
+// the rows the training-mode statistics of layer idx run over in the current forward:
+// the rows c < Tc0 (source rows 3c) of a compact layer in a compact forward, else every row
+inline int bnt_stat_rows(const KfNet *net, int idx) {
+    return (idx >= 0 && net->rs.Tc > 0 && net->layers[idx].compact) ? net->rs.Tc0 : rows_of(net, idx);
 }
 // rows a layer's activation holds in the current forward
 inline int act_rows(const KfNet *net, int idx) {

@@ -193,6 +193,8 @@ _sig(nnet, "nnet_set_bn_train", _i, _vp, _i)
 _sig(nnet, "nnet_bn_train_layers", _i, _vp, C.POINTER(_i), _i)
 _sig(nnet, "nnet_set_bn_train_sites", _i, _vp, _i)
 _sig(nnet, "nnet_bn_train_sites", _i, _vp)
+_sig(nnet, "nnet_set_bn_train_rows", _i, _vp, _i)
+_sig(nnet, "nnet_bn_train_rows", _i, _vp)
 _sig(nnet, "nnet_bn_dim", _i, _vp, C.c_char_p, _i)
 _sig(nnet, "nnet_bn_batch_stats", _i, _vp, C.c_char_p, _i, _vp, _vp)
 _sig(nnet, "nnet_bn_stats", _i, _vp, C.c_char_p, _i, C.POINTER(C.c_double), _vp, _vp)
@@ -672,7 +674,8 @@ class Network:
         check(nnet.nnet_row_set(self.h, C.byref(tc), C.byref(tc0)), "nnet_row_set")
         n, n0 = tc.value, tc0.value
         T = self.T
-        rows = np.array([3 * c if c < n0 else (T - 1) - 3 * (n - 1 - c) for c in range(n)], np.int64)
+        c = np.arange(n, dtype=np.int64)
+        rows = np.where(c < n0, 3 * c, (T - 1) - 3 * (n - 1 - c))
         return n, n0, rows
 
     def set_implicit_dz(self, on: bool):
@@ -786,6 +789,21 @@ class Network:
         """The mask set_batchnorm_train_sites set (BN_SITES' values or-ed)."""
         return nnet.nnet_bn_train_sites(self.h)
 
+    def set_batchnorm_train_rows(self, rows: str):
+        """The rows a training-mode BatchNorm of a row-subsampled layer takes its statistics from
+        (kf_nnet.h nnet_set_bn_train_rows): "all" (the default: the mode and
+        set_row_subsampling(3) refuse each other) or "subsampled" (they combine; in a forward on the
+        compact rows the statistics run over the rows 0 (mod 3), as Kaldi's do). Refused while both
+        modes are on."""
+        if rows not in BN_ROWS:
+            raise KfError(f"batchnorm train rows: unknown policy {rows!r} (one of {', '.join(BN_ROWS)})")
+        check(nnet.nnet_set_bn_train_rows(self.h, BN_ROWS[rows]), "nnet_set_bn_train_rows")
+
+    def batchnorm_train_rows(self) -> str:
+        """The policy set_batchnorm_train_rows set: "all" or "subsampled"."""
+        v = nnet.nnet_bn_train_rows(self.h)
+        return next(k for k, x in BN_ROWS.items() if x == v)
+
     def batchnorm_train_layers(self) -> list:
         """Names of the layers whose BatchNorm the switch governs under the current sites (the
         tdnnf-layers by default), in layer order."""
@@ -843,6 +861,8 @@ class Network:
 
 # the sites of training-mode BatchNorm (kf_nnet.h KF_BN_SITE_*)
 BN_SITES = {"tdnnf": 1, "conv": 2, "prefinal": 4, "batchnorm": 8, "all": 15}
+# the row policies of training-mode BatchNorm under row subsampling (kf_nnet.h KF_BN_ROWS_*)
+BN_ROWS = {"all": 0, "subsampled": 1}
 
 
 def bn_sites_mask(sites) -> int:
@@ -1035,6 +1055,9 @@ _sig(core, "kf_bn_block_stats", _i, _vp, _ll, _i, _i, _i, _f, _f, _vp, _vp, _vp,
 _sig(core, "kf_bn_block_bwd_stats", _i, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _f, _vp, _vp)
 _sig(core, "kf_bn_train_bwd_apply", _i, _vp, _ll, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _ll, _vp, _vp, _ll,
      _vp, _ll)
+_sig(core, "kf_bn_train_bwd_stats_rows", _i, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _f, _vp, _ll, _vp, _vp, _vp)
+_sig(core, "kf_bn_train_bwd_apply_rows", _i, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _ll, _vp, _vp,
+     _ll, _vp, _ll)
 _sig(core, "kf_specaug_rows", _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint64, _ll)
 _sig(core, "kf_specaug_apply", _i, _vp, _ll, _vp, _ll, _ll, _i, _vp)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)

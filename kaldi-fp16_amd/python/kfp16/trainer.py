@@ -24,6 +24,9 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
                                      on the sites TrainConfig.batchnorm_train_sites names (the
                                      TDNN-F layers by default; batch statistics, exact backward,
                                      the accumulators commit_batchnorm() later freezes)
+  1d. (TrainConfig.row_subsampling)  -> Network.set_row_subsampling(3): the layers above the conv
+                                     stack run on the rows the objective reads, which then takes
+                                     the output and writes its gradient in compact rows
   5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
                                      ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
@@ -95,6 +98,16 @@ class TrainConfig:
     # DESIGN §27): "tdnnf", "conv", "prefinal", "batchnorm", comma-separated, or "all" (what Kaldi
     # does). With the default nothing more than before is called.
     batchnorm_train_sites: str = "tdnnf"
+    # batchnorm_train_rows: Network.set_batchnorm_train_rows: "all" or "subsampled";
+    # the latter is what lets batchnorm_train and row_subsampling be on together. With the default
+    # nothing more than before is called.
+    batchnorm_train_rows: str = "all"
+    # row_subsampling: the row-subsampled step (Network.set_row_subsampling(3) at construction; a
+    # topology it does not cover raises there). A step whose subsampling_factor is 3 and whose egs
+    # all have their first supervised row at 0 (mod 3) runs the objective on the compact rows; any
+    # other batch takes that one step on all rows (counted in EgsTrainer.full_row_steps).
+    # False: nothing is called, as before.
+    row_subsampling: bool = False
     # xent_regularize: Kaldi's --chain.xent-regularize (the recipes use 0.1). > 0: the
     # value goes into the objective's options, Chain.xent writes the output-xent layer's gradient
     # from the numerator posteriors and the backward takes both seeds; result() then also
@@ -202,6 +215,11 @@ class EgsTrainer:
             self.net.set_dropout(True, (int(self.cfg.dropout_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
         if self.cfg.spec_augment:
             self.net.set_spec_augment(True, (int(self.cfg.spec_augment_seed) + 0x9E3779B97F4A7C15 * int(rank)) % 2 ** 64)
+        if self.cfg.batchnorm_train_rows != "all":
+            self.net.set_batchnorm_train_rows(self.cfg.batchnorm_train_rows)
+        self.full_row_steps = 0  # steps row_subsampling ran on all rows (a batch off the 0 (mod 3) grid, a T too short)
+        if self.cfg.row_subsampling:
+            self.net.set_row_subsampling(3)
         if self.cfg.batchnorm_train:
             if self.cfg.batchnorm_train_sites != "tdnnf":
                 self.net.set_batchnorm_train_sites(self.cfg.batchnorm_train_sites)
@@ -223,10 +241,9 @@ class EgsTrainer:
             batch.features_to_device(self.feat.ptr, 40, self.ivec.ptr)
         else:
             batch.features_to_device(self.feat.ptr, 40)
-        # rows the objective does not write must be zero for this batch
-        core.bridge_gpu_memset(self.grad_out.ptr, 0, T * self.P * 2)
-        if self.xent_grad is not None:
-            core.bridge_gpu_memset(self.xent_grad.ptr, 0, T * self.P * 2)
+        rsub = self.cfg.row_subsampling
+        if not rsub:
+            self._zero_grads(T)
         seq = np.append(np.asarray(batch.frame_offsets, np.int32), np.int32(T))
         if self.cfg.dropout_schedule:
             if fraction is None:
@@ -236,14 +253,31 @@ class EgsTrainer:
             self.net.set_dropout_proportion(dropout_proportion(self.cfg.dropout_schedule, fraction))
         if (self.cfg.dropout_schedule or self.cfg.spec_augment) and not self.ivec_dim:
             self.net.set_sequences(seq)
+        row0, frames = chain_rows(batch.frame_offsets, batch.num_frames, batch.frames_per_seq,
+                                  self.cfg.subsampling_factor, self.cfg.left_context)
+        # row subsampling declares that the objective reads rows 0 (mod 3) only: a batch that does
+        # not keep to that takes this one step on all rows
+        aligned = rsub and self.cfg.subsampling_factor == 3 and bool(np.all(row0 % 3 == 0))
+        if rsub and not aligned:
+            self.net.set_row_subsampling(0)
         if self.ivec_dim:
             self.net.forward_ivector(self.feat.ptr, T, self.ivec.ptr, seq)
         else:
             self.net.forward(self.feat.ptr, T)
+        if rsub and not aligned:
+            self.net.set_row_subsampling(3)
         num = _chain.NumBatch(batch.num_fsts())
-        row0, frames = chain_rows(batch.frame_offsets, batch.num_frames, batch.frames_per_seq,
-                                  self.cfg.subsampling_factor, self.cfg.left_context)
-        self.objective.compute(num, self.out_ptr, self.P, T, row0, frames, self.cfg.subsampling_factor,
+        # the objective's layout: the forward's frames, or with a compact row set (tc > 0; 0: a T
+        # too short for one) its tc rows, where compact row c is frame 3c for every supervised row
+        obj_rows, obj_row0, obj_stride = T, row0, self.cfg.subsampling_factor
+        if rsub:
+            tc, _tc0, _ = self.net.row_set()
+            if aligned and tc:
+                obj_rows, obj_row0, obj_stride = tc, (row0 // 3).astype(np.int32), 1
+            else:
+                self.full_row_steps += 1
+            self._zero_grads(obj_rows)
+        self.objective.compute(num, self.out_ptr, self.P, obj_rows, obj_row0, frames, obj_stride,
                                self.grad_out.ptr, self.P, self.opts)
         self._num = num  # kept alive until the stream has consumed it
         if self.xent_grad is not None:
@@ -261,6 +295,12 @@ class EgsTrainer:
         self.steps += 1
         if self.cfg.orthonormal_every > 0 and self.steps % self.cfg.orthonormal_every == 0:
             self.net.constrain_orthonormal()
+
+    def _zero_grads(self, rows: int):
+        # rows the objective does not write must be zero for this batch
+        core.bridge_gpu_memset(self.grad_out.ptr, 0, rows * self.P * 2)
+        if self.xent_grad is not None:
+            core.bridge_gpu_memset(self.xent_grad.ptr, 0, rows * self.P * 2)
 
     def result(self):
         """The objective's KfChainResult of the last step; with xent_regularize > 0 it also has
