@@ -108,6 +108,28 @@ int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
                      const void *nnet_output, long long ld, long long num_rows, int nseq,
                      const int32_t *seq_row0, const int32_t *seq_frames, int stride,
                      void *out_grad, long long ldg);
+/* kf_chain_compute with the weights a Kaldi eg carries; kf_chain_compute is
+ * this call with both pointers NULL.
+ *   seq_weight   host [nseq], the example's <Weight>; NULL = ones. Sequence i runs with
+ *                w_i = opts->supervision_weight * seq_weight[i] wherever kf_chain_compute uses
+ *                supervision_weight: the objective, the -10 w_i T of a not-finite sequence, the
+ *                numerator and denominator terms of the gradient, the L2 term and its
+ *                statistic, and w_i T in the statistics. The out-of-range penalty is not scaled.
+ *   frame_weight host [sum_i seq_frames[i]], sequence after sequence: Kaldi's per-frame deriv
+ *                weights (<DW>/<DW2>, --apply-deriv-weights); NULL = ones. With d the fp32
+ *                derivative of an element (every term in), the row is written as
+ *                rne_fp16(-(d * f)): NnetChainTrainer's MulRowsVec, one multiply and then the
+ *                one rounding. No statistic depends on f, as in Kaldi.
+ * Every weight must be finite and >= 0: anything else is an error that names the sequence (and
+ * frame) and launches nothing. Weight 0 is legal. The weights are uploaded with every call (they
+ * change with every batch; the layout cache does not cover them), through the pinned staging
+ * slot of the layout and one asynchronous copy on the stream: no allocation per step, no host
+ * stall. With all weights exactly 1.0 every output is bit-identical to kf_chain_compute. */
+int kf_chain_compute_weighted(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
+                              const void *nnet_output, long long ld, long long num_rows, int nseq,
+                              const int32_t *seq_row0, const int32_t *seq_frames, int stride,
+                              void *out_grad, long long ldg, const float *seq_weight,
+                              const float *frame_weight);
 /* Device array of per-sequence statistics of the last compute:
  * float[8] per sequence {num_lp, den_lp, objf, l2_term, weight*frames, frames, oor, ok}. */
 const float *kf_chain_seq_stats(const KfChain *c);
@@ -124,7 +146,10 @@ int kf_chain_result(KfChain *c, KfChainResult *out);
  * with post the posteriors of the in-range pdfs as a dense row and S their computed sum,
  *   xent_grad[p] = rne_fp16(-xent_regularize * w * (post[p] - exp(y[p]) * S))
  * (zeros for a sequence whose objective was not finite, and with xent_regularize == 0), and per
- * sequence objf = w * sum_t sum_p post[p] * y[p] (0 when not finite). Every supervised row's
+ * sequence objf = w * sum_t sum_p post[p] * y[p] (0 when not finite). After a
+ * kf_chain_compute_weighted the call uses that compute's weights: w is w_i, and the row is
+ * rne_fp16(f * v) with v the fp32 value above before its rounding; the objective does not
+ * depend on f (Kaldi takes it before the row scaling). Every supervised row's
  * first P columns are written exactly once; nothing else is touched. A call replays bit for
  * bit. 0 / -1: no compute before it, another batch than that compute's, ldx or ldg below P,
  * a NULL pointer. */

@@ -171,6 +171,17 @@ typedef struct {
 
 int kf_egs_batch_info(const KfEgsBatch *b, KfEgsBatchInfo *out);
 const char *kf_egs_batch_key(const KfEgsBatch *b, int i);
+/* The weights the examples carry, for kf_chain_compute_weighted (kf_chain.h);
+ * host only, and no part of KfEgsBatchInfo (whose `weight` stays the first example's).
+ * kf_egs_batch_weights: each example's <Weight>.
+ * kf_egs_batch_deriv_weights: each example's per-frame deriv weights (<DW> / <DW2>),
+ * frames_per_seq[i] of them, example after example; an example without a block gives ones.
+ * *any (may be NULL) = 1 when at least one example had a block. -1, naming the example's key,
+ * for an example whose count is neither 0 nor its frames_per_seq, or that carries weights with
+ * num_sequences != 1 (theirs are frame-major across sequences; the batch layout has one
+ * sequence per example). */
+int kf_egs_batch_weights(const KfEgsBatch *b, float *out /* [B] */);
+int kf_egs_batch_deriv_weights(const KfEgsBatch *b, float *out /* [sum frames_per_seq] */, int *any);
 /* Host reference merge: fp32 features / ivectors as batch.NewBatch builds them. */
 int kf_egs_batch_features_host(const KfEgsBatch *b, float *out /* [total_frames x feat_dim] */);
 int kf_egs_batch_ivectors_host(const KfEgsBatch *b, float *out /* [B x ivector_dim] */);

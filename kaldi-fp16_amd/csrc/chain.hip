@@ -97,6 +97,11 @@ struct KfChain {
     long long *d_row0 = nullptr;
     int *d_frames = nullptr;
     float *d_num_total = nullptr;
+    // kf_chain_compute_weighted: [max_seqs] and [max_seqs][max_frames] behind the
+    // frame counts, in the same allocation and staging slot; which of them the last compute
+    // used (kf_chain_xent uses the same)
+    float *d_seq_w = nullptr, *d_frame_w = nullptr;
+    bool use_seq_w = false, use_frame_w = false;
     ChainLayoutKey last;          // cache of the last run's layout
     // pinned staging of the layout upload: two slots, each reused after its copy's event
     char *h_stage[2] = {nullptr, nullptr};
@@ -312,6 +317,13 @@ extern "C" void kf_num_batch_free(KfNumBatch *b) {
     kf_take_pending("the return of kf_num_batch_free");
 }
 
+// bytes of the layout (descriptors, row offsets, frame counts) and of the whole staging slot,
+// which carries the weights of a weighted compute behind it
+static size_t layout_bytes(int max_seqs) { return (size_t)max_seqs * (sizeof(LogFstDev) + 12); }
+static size_t slot_bytes(int max_seqs, int max_frames) {
+    return layout_bytes(max_seqs) + (size_t)max_seqs * 4 + (size_t)max_seqs * max_frames * 4;
+}
+
 extern "C" KfChain *kf_chain_create(const KfDenGraph *den, int max_seqs, int max_frames) {
     if (!den || max_seqs <= 0 || max_frames <= 0) {
         kfc_set_error("kf_chain_create: invalid arguments");
@@ -329,11 +341,14 @@ extern "C" KfChain *kf_chain_create(const KfDenGraph *den, int max_seqs, int max
     ok = ok && hipMalloc(&c->bsum_store, (size_t)max_seqs * (max_frames + 1) * 4) == hipSuccess;
     ok = ok && hipMalloc(&c->stats, (size_t)max_seqs * 8 * 4) == hipSuccess;
     // descriptors, row offsets and frame counts in one allocation, laid out as the pinned
-    // staging slot, so a layout change is one copy
-    ok = ok && hipMalloc(&c->d_desc, (size_t)max_seqs * (sizeof(LogFstDev) + 12)) == hipSuccess;
+    // staging slot, so a layout change is one copy; the sequence and frame weights of a
+    // weighted compute behind them
+    ok = ok && hipMalloc(&c->d_desc, slot_bytes(max_seqs, max_frames)) == hipSuccess;
     if (ok) {
         c->d_row0 = reinterpret_cast<long long *>(reinterpret_cast<char *>(c->d_desc) + (size_t)max_seqs * sizeof(LogFstDev));
         c->d_frames = reinterpret_cast<int *>(reinterpret_cast<char *>(c->d_row0) + (size_t)max_seqs * 8);
+        c->d_seq_w = reinterpret_cast<float *>(reinterpret_cast<char *>(c->d_desc) + layout_bytes(max_seqs));
+        c->d_frame_w = c->d_seq_w + max_seqs;
     }
     ok = ok && hipMalloc(&c->d_num_total, (size_t)max_seqs * 4) == hipSuccess;
     ok = ok && hipMalloc(&c->den_out, (size_t)max_seqs * 8) == hipSuccess;
@@ -342,8 +357,7 @@ extern "C" KfChain *kf_chain_create(const KfDenGraph *den, int max_seqs, int max
     ok = ok && hipEventCreateWithFlags(&c->ev_num, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i < 2; ++i) {
         ok = ok && hipEventCreateWithFlags(&c->ev_stage[i], hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipHostMalloc((void **)&c->h_stage[i], (size_t)max_seqs * (sizeof(LogFstDev) + 12), 0) ==
-                       hipSuccess;
+        ok = ok && hipHostMalloc((void **)&c->h_stage[i], slot_bytes(max_seqs, max_frames), 0) == hipSuccess;
     }
     if (!ok) {
         delete c;
@@ -362,7 +376,8 @@ extern "C" void kf_chain_free(KfChain *c) {
 // ---- kf_chain_compute, step by step -----------------------------------------
 static bool compute_args_ok(const KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
                             const void *nnet_output, long long ld, int nseq, const int32_t *seq_row0,
-                            const int32_t *seq_frames, int stride, const void *out_grad, long long ldg) {
+                            const int32_t *seq_frames, int stride, const void *out_grad, long long ldg,
+                            const float *seq_w, const float *frame_w) {
     if (!c || !num || !opts || !nnet_output || !out_grad || !seq_row0 || !seq_frames) {
         kfc_set_error("kf_chain_compute: NULL argument");
         return false;
@@ -374,14 +389,33 @@ static bool compute_args_ok(const KfChain *c, const KfNumBatch *num, const KfCha
                       nseq, c->max_seqs, num->nd->desc.size(), stride, ld, ldg, P);
         return false;
     }
+    // every weight finite and >= 0 (0 is legal); the frame weights lie sequence after sequence
+    for (int i = 0; seq_w && i < nseq; ++i)
+        if (!(seq_w[i] >= 0.0f) || std::isinf(seq_w[i])) {
+            kfc_set_error("kf_chain_compute_weighted: sequence %d: weight %g is not finite and >= 0", i, seq_w[i]);
+            return false;
+        }
+    if (frame_w) {
+        const float *fw = frame_w;
+        for (int i = 0; i < nseq; fw += std::max(seq_frames[i], 0), ++i)
+            for (int t = 0; t < seq_frames[i]; ++t)
+                if (!(fw[t] >= 0.0f) || std::isinf(fw[t])) {
+                    kfc_set_error("kf_chain_compute_weighted: sequence %d, frame %d: deriv weight %g is not "
+                                  "finite and >= 0", i, t, fw[t]);
+                    return false;
+                }
+    }
     return true;
 }
 
 // A new layout: range checks, the numerator buffers grown, the descriptors filled and
-// uploaded with the row offsets and frame counts, the cache key set. False with the error set.
+// uploaded with the row offsets and frame counts, the cache key set. The weights of a weighted
+// compute ride in the same slot and copy (that compute comes here every time: the cache key
+// does not cover them). False with the error set.
 static bool layout_update(KfChain *c, const KfNumBatch *num, const void *nnet_output, long long ld,
                           long long num_rows, int nseq, const int32_t *seq_row0,
-                          const int32_t *seq_frames, int stride, hipStream_t st) {
+                          const int32_t *seq_frames, int stride, const float *seq_w, const float *frame_w,
+                          hipStream_t st) {
     for (int i = 0; i < nseq; ++i)
         if (seq_frames[i] < 0 || seq_frames[i] > c->max_frames || seq_row0[i] < 0 ||
             (seq_frames[i] > 0 &&
@@ -448,8 +482,20 @@ static bool layout_update(KfChain *c, const KfNumBatch *num, const void *nnet_ou
     memcpy(hs_, c->host_desc.data(), nseq * sizeof(LogFstDev));
     memcpy(hs_ + (size_t)c->max_seqs * sizeof(LogFstDev), r0.data(), nseq * 8);
     memcpy(hs_ + (size_t)c->max_seqs * (sizeof(LogFstDev) + 8), seq_frames, nseq * 4);
-    bool cp = hipMemcpyAsync(c->d_desc, hs_, (size_t)c->max_seqs * (sizeof(LogFstDev) + 12),
-                             hipMemcpyHostToDevice, st) == hipSuccess;
+    size_t nbytes = layout_bytes(c->max_seqs);
+    if (seq_w || frame_w) {
+        float *hw = reinterpret_cast<float *>(hs_ + nbytes);
+        for (int i = 0; i < nseq; ++i) hw[i] = seq_w ? seq_w[i] : 1.0f;
+        nbytes += (size_t)c->max_seqs * 4;
+        if (frame_w) {  // [nseq][max_frames]; only a sequence's first frames[i] are read
+            float *hf = hw + c->max_seqs;
+            const float *fw = frame_w;
+            for (int i = 0; i < nseq; fw += seq_frames[i], ++i)
+                memcpy(hf + (size_t)i * c->max_frames, fw, (size_t)seq_frames[i] * 4);
+            nbytes += (size_t)nseq * c->max_frames * 4;
+        }
+    }
+    bool cp = hipMemcpyAsync(c->d_desc, hs_, nbytes, hipMemcpyHostToDevice, st) == hipSuccess;
     cp = cp && hipEventRecord(c->ev_stage[slot], st) == hipSuccess;
     if (!cp) {
         c->last.gen = 0;
@@ -517,6 +563,8 @@ static bool launch_denominator(KfChain *c, const KfChainOpts *opts, const void *
     r.out_grad = (h16 *)out_grad;
     r.ldg = ldg;
     r.opts = *opts;
+    r.seq_w = c->use_seq_w ? c->d_seq_w : nullptr;
+    r.frame_w = c->use_frame_w ? c->d_frame_w : nullptr;
     // algorithmic bytes: per frame three streamed passes over the
     // packed arc records, alpha' stored and re-read, the output row read twice
     // and the gradient row written once
@@ -539,20 +587,27 @@ static bool launch_denominator(KfChain *c, const KfChainOpts *opts, const void *
     return true;
 }
 
-extern "C" int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
-                                const void *nnet_output, long long ld, long long num_rows, int nseq,
-                                const int32_t *seq_row0, const int32_t *seq_frames, int stride,
-                                void *out_grad, long long ldg) {
+extern "C" int kf_chain_compute_weighted(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
+                                         const void *nnet_output, long long ld, long long num_rows, int nseq,
+                                         const int32_t *seq_row0, const int32_t *seq_frames, int stride,
+                                         void *out_grad, long long ldg, const float *seq_weight,
+                                         const float *frame_weight) {
     kf_take_pending(__func__);
-    if (!compute_args_ok(c, num, opts, nnet_output, ld, nseq, seq_row0, seq_frames, stride, out_grad, ldg))
+    if (!compute_args_ok(c, num, opts, nnet_output, ld, nseq, seq_row0, seq_frames, stride, out_grad, ldg,
+                         seq_weight, frame_weight))
         return -1;
     hipStream_t st = kf_stream();
     c->xent_ran = false;
     // a refilled numerator batch (kf_num_batch_refill): its copy lands before anything reads it
     if (num->ev_copy) hipStreamWaitEvent(st, num->ev_copy, 0);
-    if (!c->last.matches(num->gen, nseq, stride, nnet_output, ld, num_rows, seq_row0, seq_frames) &&
-        !layout_update(c, num, nnet_output, ld, num_rows, nseq, seq_row0, seq_frames, stride, st))
+    // weights change with every batch: a weighted compute uploads them (with the layout) every time
+    const bool weighted = seq_weight || frame_weight;
+    if ((weighted || !c->last.matches(num->gen, nseq, stride, nnet_output, ld, num_rows, seq_row0, seq_frames)) &&
+        !layout_update(c, num, nnet_output, ld, num_rows, nseq, seq_row0, seq_frames, stride, seq_weight,
+                       frame_weight, st))
         return -1;
+    c->use_seq_w = seq_weight != nullptr;
+    c->use_frame_w = frame_weight != nullptr;
     launch_numerator(c, nnet_output, ld, nseq, seq_frames, st);
     if (!launch_denominator(c, opts, nnet_output, ld, nseq, seq_frames, stride, out_grad, ldg, st)) return -1;
     if (hipGetLastError() != hipSuccess) {
@@ -560,6 +615,14 @@ extern "C" int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChain
         return -1;
     }
     return 0;
+}
+
+extern "C" int kf_chain_compute(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
+                                const void *nnet_output, long long ld, long long num_rows, int nseq,
+                                const int32_t *seq_row0, const int32_t *seq_frames, int stride,
+                                void *out_grad, long long ldg) {
+    return kf_chain_compute_weighted(c, num, opts, nnet_output, ld, num_rows, nseq, seq_row0, seq_frames, stride,
+                                     out_grad, ldg, nullptr, nullptr);
 }
 
 // The xent output's derivative and objective (chain_xent.hip) over the layout and the numerator
@@ -612,6 +675,10 @@ extern "C" int kf_chain_xent(KfChain *c, const KfNumBatch *num, const KfChainOpt
     r.stride = c->last.stride;
     r.w = opts->supervision_weight;
     r.scale = opts->xent_regularize * opts->supervision_weight;
+    // after a weighted compute: its weights, still on the device
+    r.xr = opts->xent_regularize;
+    r.seq_w = c->use_seq_w ? c->d_seq_w : nullptr;
+    r.frame_w = c->use_frame_w ? c->d_frame_w : nullptr;
     double frames = 0;
     for (int f : c->last.frames) {
         frames += f;

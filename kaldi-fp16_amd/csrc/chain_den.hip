@@ -752,6 +752,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_post(const DenDev g, const 
         nf = &r.nums[seq];
         NG = nf->G;
         w = r.opts.supervision_weight;
+        if (r.seq_w) w *= r.seq_w[seq];  // w_i, block-uniform
         const float num_lp = *nf->total;
         const float den_lp = r.den_out[seq * 2 + 1];
         double objf = (double)w * ((double)num_lp - (double)den_lp);
@@ -766,7 +767,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_post(const DenDev g, const 
             st8[7] = ok ? 1.0f : 0.0f;
         }
     }
-    const float l2s = r.opts.supervision_weight * r.opts.l2_regularize;
+    const float l2s = w * r.opts.l2_regularize;
     const float oscale = 2.0f * r.opts.out_of_range_regularize;
     const bool do_oor = MODE == DEN_PRODUCT && r.opts.out_of_range_regularize > 0.0f;
     const bool do_l2 = MODE == DEN_PRODUCT && r.opts.l2_regularize > 0.0f;
@@ -868,6 +869,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_post(const DenDev g, const 
                 const XT *xrow = nnet + (row0 + (long long)tf * r.stride) * r.ld;
                 h16 *orow = r.out_grad + (row0 + (long long)tf * r.stride) * r.ldg;
                 const bool even = (tf & 1) == 0;
+                // the frame's deriv weight, one block-uniform load (Kaldi's MulRowsVec, after
+                // every term is in): one fp32 multiply, then the one rounding
+                const float fw = r.frame_w ? r.frame_w[(size_t)seq * r.max_frames + tf] : 1.0f;
                 for (int pdf = tid; pdf < P; pdf += DEN_THREADS) {
                     const float x = (float)xrow[pdf];
                     float d = 0.0f;
@@ -885,7 +889,7 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_post(const DenDev g, const 
                         d -= l2s * x;
                         sq += x * x;
                     }
-                    orow[pdf] = ok ? (h16)(-d) : (h16)0.0f;  // loss gradient = -deriv
+                    orow[pdf] = ok ? (h16)(-(d * fw)) : (h16)0.0f;  // loss gradient = -deriv
                 }
             }
             __syncthreads();

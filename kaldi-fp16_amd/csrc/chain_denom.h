@@ -60,6 +60,9 @@ struct DenRun {
     h16 *out_grad;
     long long ldg;
     KfChainOpts opts;
+    // kf_chain_compute_weighted, null = ones
+    const float *seq_w;     // [nseq] the example's weight (times opts.supervision_weight)
+    const float *frame_w;   // [nseq][max_frames] deriv weight of (sequence, frame)
 };
 
 enum { DEN_ABI = 0, DEN_PRODUCT = 1 };

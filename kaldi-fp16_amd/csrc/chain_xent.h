@@ -22,6 +22,10 @@ struct XentRun {
     int max_t;               // frames of the longest sequence: block b is frame b % max_t of sequence b / max_t
     int P, stride;
     float w, scale;          // supervision weight, xent_regularize * w
+    // after a kf_chain_compute_weighted, null = ones
+    float xr;                // xent_regularize: with seq_w, scale = xr * (w * seq_w[i])
+    const float *seq_w;      // [nseq]
+    const float *frame_w;    // [nseq][part_ld]
 };
 
 // total_frames = all supervised frames (the profile record's bytes)

@@ -2,7 +2,8 @@
 // kf_chain_compute left behind (kf_chain.h kf_chain_xent): Kaldi's chain training
 // with --chain.xent-regularize. For a supervised row, with post the numerator posteriors as
 // a dense row (out-of-range pdfs dropped) and S their computed sum,
-//   grad[p] = rne(-xr w (post[p] - exp(y[p]) S))    objf += w post[p] y[p]
+//   grad[p] = rne(f (-xr w (post[p] - exp(y[p]) S)))    objf += w post[p] y[p]
+// (w = w_i and f the frame's deriv weight after a weighted compute; else f = 1)
 // i.e. the posteriors scaled by the supervision weight (Kaldi's xent_output_deriv) taken
 // back through the log-softmax (LogSoftmaxComponent::Backprop), as a loss gradient.
 // One workgroup per (sequence, frame), as k_den_post's product mode handles the same sparse
@@ -62,7 +63,12 @@ __global__ __launch_bounds__(XENT_THREADS) void k_chain_xent(const XentRun r) {
         if (p > 0 && p <= P) sp += nps[q];
     }
     const float S = block_sum<XENT_WAVES>(sp, red_s);
-    const float scale = r.scale;
+    float w = r.w, scale = r.scale;
+    if (r.seq_w) {  // the weighted compute's w_i, block-uniform
+        w = r.w * r.seq_w[seq];
+        scale = r.xr * w;
+    }
+    const float fw = r.frame_w ? r.frame_w[(size_t)seq * r.part_ld + t] : 1.0f;
     const bool zero = !(scale != 0.0f);
     float ob = 0.f;
     for (int c0 = 0; c0 < P; c0 += XENT_CHUNK) {
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(XENT_THREADS) void k_chain_xent(const XentRun r) {
                 for (int e = 0; e < 8; ++e) {
                     const float po = e < 4 ? p0[e & 3] : p1[e & 3], yf = (float)yv[e];
                     if (po != 0.f) ob += po * yf;
-                    o[e] = zero ? (h16)0.0f : f2h(-scale * (po - __expf(yf) * S));
+                    o[e] = zero ? (h16)0.0f : f2h(fw * (-scale * (po - __expf(yf) * S)));
                 }
                 store_h8(g + c0 + j8, o);
             }
@@ -96,13 +102,13 @@ __global__ __launch_bounds__(XENT_THREADS) void k_chain_xent(const XentRun r) {
             for (int j = tid; j < n; j += XENT_THREADS) {
                 const float po = row[j], yf = (float)y[c0 + j];
                 if (po != 0.f) ob += po * yf;
-                g[c0 + j] = zero ? (h16)0.0f : f2h(-scale * (po - __expf(yf) * S));
+                g[c0 + j] = zero ? (h16)0.0f : f2h(fw * (-scale * (po - __expf(yf) * S)));
             }
         }
         __syncthreads();  // the next chunk's zero fill
     }
     const float o = block_sum<XENT_WAVES>(ob, red_o);
-    if (tid == 0) r.part[(size_t)seq * r.part_ld + t] = r.w * o;
+    if (tid == 0) r.part[(size_t)seq * r.part_ld + t] = w * o;
 }
 
 void launch_chain_xent(const XentRun &r, int nseq, double total_frames) {

@@ -1247,6 +1247,46 @@ const char *kf_egs_batch_key(const KfEgsBatch *b, int i) {
     return b->ex[i].key.c_str();
 }
 
+// The weights the examples carry (kf_chain_compute_weighted's seq_weight / frame_weight):
+// NnetChainSupervision's weight and deriv_weights, which Kaldi's trainer applies
+// (NnetChainTrainer::ProcessOutputs, --apply-deriv-weights).
+int kf_egs_batch_weights(const KfEgsBatch *b, float *out) {
+    if (!b || !out) {
+        set_err("kf_egs_batch_weights: null argument");
+        return -1;
+    }
+    for (size_t i = 0; i < b->ex.size(); i++) out[i] = b->ex[i].weight;
+    return 0;
+}
+
+int kf_egs_batch_deriv_weights(const KfEgsBatch *b, float *out, int *any) {
+    if (!b || !out) {
+        set_err("kf_egs_batch_deriv_weights: null argument");
+        return -1;
+    }
+    int have = 0;
+    for (size_t i = 0; i < b->ex.size(); i++) {
+        const ExOwned &e = b->ex[i];
+        const int fps = std::max(0, b->fps[i]);
+        if (e.dw.empty()) {
+            std::fill(out, out + fps, 1.0f);
+        } else if (e.nseq != 1) {
+            set_err("example %zu (%s): deriv weights with num_sequences=%d (one sequence per example here)", i,
+                    e.key.c_str(), e.nseq);
+            return -1;
+        } else if ((int)e.dw.size() != fps) {
+            set_err("example %zu (%s): %zu deriv weights, frames_per_seq=%d", i, e.key.c_str(), e.dw.size(), fps);
+            return -1;
+        } else {
+            std::copy(e.dw.begin(), e.dw.end(), out);
+            have = 1;
+        }
+        out += fps;
+    }
+    if (any) *any = have;
+    return 0;
+}
+
 int kf_egs_batch_features_host(const KfEgsBatch *b, float *out) {
     if (!b || !out) {
         set_err("kf_egs_batch_features_host: null argument");

@@ -67,6 +67,8 @@ _sig("kf_num_batch_free", None, _vp)
 _sig("kf_chain_create", _vp, _vp, _i, _i)
 _sig("kf_chain_free", None, _vp)
 _sig("kf_chain_compute", _i, _vp, _vp, C.POINTER(KfChainOpts), _vp, _ll, _ll, _i, _vp, _vp, _i, _vp, _ll)
+_sig("kf_chain_compute_weighted", _i, _vp, _vp, C.POINTER(KfChainOpts), _vp, _ll, _ll, _i, _vp, _vp, _i, _vp, _ll,
+     _vp, _vp)
 _sig("kf_chain_seq_stats", _vp, _vp)
 _sig("kf_chain_result", _i, _vp, C.POINTER(KfChainResult))
 _sig("kf_chain_xent", _i, _vp, _vp, C.POINTER(KfChainOpts), _vp, _ll, _vp, _ll)
@@ -199,10 +201,28 @@ class Chain:
             _raise("kf_chain_create")
 
     def compute(self, num: NumBatch, nnet_ptr, ld, num_rows, seq_row0, seq_frames, stride,
-                out_grad_ptr, ldg, opts: KfChainOpts | None = None):
+                out_grad_ptr, ldg, opts: KfChainOpts | None = None, seq_weight=None, frame_weight=None):
+        """seq_weight [nseq] (each example's <Weight>) and frame_weight [sum seq_frames] (Kaldi's
+        deriv weights, sequence after sequence): either one given makes this
+        kf_chain_compute_weighted; a later xent() uses the same weights."""
         opts = opts or KfChainOpts.default()
         self._r0 = _a(seq_row0, np.int32)
         self._fr = _a(seq_frames, np.int32)
+        if seq_weight is not None or frame_weight is not None:
+            sw = None if seq_weight is None else _a(seq_weight, np.float32).reshape(-1)
+            fw = None if frame_weight is None else _a(frame_weight, np.float32).reshape(-1)
+            if sw is not None and len(sw) != len(self._r0):
+                raise KfError(f"kf_chain_compute_weighted: {len(sw)} sequence weights for {len(self._r0)} sequences")
+            if fw is not None and len(fw) != int(self._fr.clip(min=0).sum()):
+                raise KfError(f"kf_chain_compute_weighted: {len(fw)} frame weights for "
+                              f"{int(self._fr.clip(min=0).sum())} frames")
+            rc = core.kf_chain_compute_weighted(self.h, num.h, C.byref(opts), nnet_ptr, ld, num_rows, len(self._r0),
+                                                self._r0.ctypes.data, self._fr.ctypes.data, stride, out_grad_ptr,
+                                                ldg, None if sw is None else sw.ctypes.data,
+                                                None if fw is None else fw.ctypes.data)
+            if rc != 0:
+                _raise("kf_chain_compute_weighted")
+            return
         rc = core.kf_chain_compute(self.h, num.h, C.byref(opts), nnet_ptr, ld, num_rows, len(self._r0),
                                    self._r0.ctypes.data, self._fr.ctypes.data, stride,
                                    out_grad_ptr, ldg)

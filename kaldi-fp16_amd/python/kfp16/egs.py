@@ -90,6 +90,8 @@ _sig("kf_egs_loader_num_files", _i, _vp)
 _sig("kf_egs_loader_free", None, _vp)
 _sig("kf_egs_batch_info", _i, _vp, C.POINTER(KfEgsBatchInfo))
 _sig("kf_egs_batch_key", C.c_char_p, _vp, _i)
+_sig("kf_egs_batch_weights", _i, _vp, _vp)
+_sig("kf_egs_batch_deriv_weights", _i, _vp, _vp, C.POINTER(_i))
 _sig("kf_egs_batch_features_host", _i, _vp, _vp)
 _sig("kf_egs_batch_ivectors_host", _i, _vp, _vp)
 _sig("kf_egs_batch_features", _i, _vp, _vp, _i, _vp)
@@ -350,6 +352,21 @@ class TrainingBatch:
                             dst=_arr(info.per_col, A, np.int32),
                             final_state=_arr(info.per_final_state, F, np.int32))
         self.keys = [lib.kf_egs_batch_key(handle, i).decode() for i in range(B)]
+        # each example's <Weight> (`weight` above is the first example's, as the reference keeps it)
+        self.example_weights = np.zeros(B, np.float32)
+        if lib.kf_egs_batch_weights(handle, self.example_weights.ctypes.data) != 0:
+            raise EgsError(last_error())
+
+    def deriv_weights(self):
+        """(weights, any): the examples' per-frame deriv weights (<DW> / <DW2>), frames_per_seq[i]
+        each, example after example, ones for an example without a block; any = some example had
+        one. EgsError (naming the key) for a count that is not frames_per_seq, or weights on an
+        example of several sequences."""
+        out = np.ones(max(int(self.frames_per_seq.clip(min=0).sum()), 1), np.float32)
+        any_ = _i()
+        if lib.kf_egs_batch_deriv_weights(self._h, out.ctypes.data, C.byref(any_)) != 0:
+            raise EgsError(last_error())
+        return out[:int(self.frames_per_seq.clip(min=0).sum())], bool(any_.value)
 
     def num_fsts(self) -> list:
         """Per-sequence numerator FSTs as the dicts kfp16.chain.pack_num_fsts takes."""

@@ -27,6 +27,9 @@ Restates nnet.TrainStep (internal/nnet/train_step.go:142-283) over the build's p
   1d. (TrainConfig.row_subsampling)  -> Network.set_row_subsampling(3): the layers above the conv
                                      stack run on the rows the objective reads, which then takes
                                      the output and writes its gradient in compact rows
+  2b. (TrainConfig.apply_deriv_weights, example_weights) -> the batch's per-frame deriv weights
+                                     and per-eg weights into the objective (Chain.compute's
+                                     frame_weight / seq_weight), as Kaldi's trainer applies them
   5. (TrainConfig.orthonormal_every) -> Network.constrain_orthonormal every N-th step: Kaldi's
                                      ConstrainOrthonormal on the TDNN-F bottlenecks
 plus, for data parallel, the flat-gradient all-reduce between 3 and 4 (kfp16.dp).
@@ -115,6 +118,13 @@ class TrainConfig:
     # (0.5 / xent_regularize) is the xconfig key learning-rate-factor, honoured by kaldi_update.
     # 0: the trainer makes exactly the calls it made before.
     xent_regularize: float = 0.0
+    # apply_deriv_weights: Kaldi's --apply-deriv-weights (true there): the batch's
+    # per-frame deriv weights (<DW> / <DW2>, cut to each eg's supervised frames) scale the rows of
+    # the chain derivative and of the xent derivative, inside the objective's kernels.
+    # example_weights: each eg's own <Weight> multiplies opts.supervision_weight for its sequence.
+    # Both False: the trainer makes exactly the calls it made before.
+    apply_deriv_weights: bool = False
+    example_weights: bool = False
 
 
 def parse_dropout_schedule(schedule: str):
@@ -277,8 +287,22 @@ class EgsTrainer:
             else:
                 self.full_row_steps += 1
             self._zero_grads(obj_rows)
-        self.objective.compute(num, self.out_ptr, self.P, obj_rows, obj_row0, frames, obj_stride,
-                               self.grad_out.ptr, self.P, self.opts)
+        # the weights the egs carry, by (sequence, frame): the same on either row layout
+        seq_w = frame_w = None
+        if self.cfg.example_weights:
+            seq_w = np.asarray(batch.example_weights, np.float32)
+        if self.cfg.apply_deriv_weights:
+            dw, have = batch.deriv_weights()
+            if have:  # an eg cut short keeps its first frames[i] weights
+                o = np.concatenate(([0], np.cumsum(np.maximum(batch.frames_per_seq, 0))))
+                frame_w = np.concatenate([dw[o[i]:o[i] + frames[i]] for i in range(len(frames))]
+                                         or [np.zeros(0, np.float32)]).astype(np.float32)
+        if seq_w is None and frame_w is None:
+            self.objective.compute(num, self.out_ptr, self.P, obj_rows, obj_row0, frames, obj_stride,
+                                   self.grad_out.ptr, self.P, self.opts)
+        else:
+            self.objective.compute(num, self.out_ptr, self.P, obj_rows, obj_row0, frames, obj_stride,
+                                   self.grad_out.ptr, self.P, self.opts, seq_weight=seq_w, frame_weight=frame_w)
         self._num = num  # kept alive until the stream has consumed it
         if self.xent_grad is not None:
             self.objective.xent(num, self.xent_ptr, self.P, self.xent_grad.ptr, self.P, self.opts)
