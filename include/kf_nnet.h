@@ -421,11 +421,17 @@ int nnet_set_implicit_dz(KfNet *net, int on);
  * behind the chain and any missing order shows as a wrong gradient. */
 int nnet_debug_backward(KfNet *net, int main_aff, long long stall_cycles);
 
+/* diagnostics (tests): the device blocks the net holds at this moment (-1: null net). A switch
+ * allocates what it needs when it is first set; setting it again does not grow the count. */
+int nnet_debug_alloc_count(const KfNet *net);
+
 /* diagnostics (tests): back-propagate through the top n layers only; device
  * pointer of an internal tensor ("dz0" .. "dz2", "g0" .. "g2": the backward's gradient ring,
  * "dzlast": the ring buffer the last step wrote, "dbott" (the buffer of the last
  * TDNN-F / prefinal step), "aux", "mask",
- * "bn_scale", "bn2_scale", "dproj" (attention: the gradient of its affine output), and with fp8 on "x8q" / "x8s": the e4m3 values
+ * "bn_scale", "bn2_scale", "dproj" (attention: the gradient of its affine output), "gdb" (a
+ * combine-feature-maps layer: the per-sequence gradient [B x height * num-filters2] of its second
+ * input), and with fp8 on "x8q" / "x8s": the e4m3 values
  * [T x pad128(in_dim)] and E8M0 scales [T x pad128(in_dim)/32] of the MXFP8 input copy
  * the layer's GEMM reads; "w8dq" / "w8ds": a strided TDNN-F layer's e4m3 affine weight rows
  * for its MXFP8 input gradient [bottleneck x 2*pad128(out_dim)]; "dz8q" / "dz8s" with

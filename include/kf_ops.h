@@ -173,6 +173,10 @@ int kf_gemm_fused(int M, int N, int K, const KfOperand *A, const KfOperand *B,
  */
 int kf_gemm_wgrad(int M, int N, int K, const KfOperand *A, const KfOperand *B, float *dW,
                   long long ldw, float *bias_grad, int accumulate);
+/* 1 when kf_gemm_wgrad would run this product on the 3x3 conv halo kernel (the only one that takes
+ * time-strided rows, KfOperand.tmul / t0), 0 when it would not, -1 for an invalid operand. No
+ * launch and no HIP call: a caller asks before it plans a time-strided weight gradient. */
+int kf_gemm_wgrad_halo_applies(int M, int N, int K, const KfOperand *A, const KfOperand *B);
 /* kf_gemm_wgrad, then dW[:, n] and bias_grad[n] scaled by col_scale[n] (fp32 [N]) in the
  * split-K reduction: the TDNN-F affine weight gradient on the implicit dz (a masked B
  * operand g with the BN scale applied here) */

@@ -310,6 +310,17 @@ static bool conv_wgrad_halo_plan(int M, int N, int K, const OpD &a, const OpD &b
     return true;
 }
 
+// Whether the plan covers the product (kf_ops.h kf_gemm_wgrad_halo_applies): no launch, and the
+// calling thread's kf_halo_debug_last record is left as it was.
+bool kf_conv_wgrad_halo_applies(int M, int N, int K, const OpD &a, const OpD &b) {
+    int keep[KF_HALO_DBG_N];
+    kf_halo_debug_last(keep, KF_HALO_DBG_N);
+    WHaloPlan P;
+    const bool ok = conv_wgrad_halo_plan(M, N, K, a, b, P);
+    std::copy(keep, keep + KF_HALO_DBG_N, kf_halo_dbg_begin(keep[0]));
+    return ok;
+}
+
 // Returns 1 when launched, 0 when the plan does not apply (the caller runs the im2col
 // GEMM), -1 on error.
 int kf_conv_wgrad_halo_try(int M, int N, int K, const OpD &a, const OpD &b, float *dW, long long ldw,

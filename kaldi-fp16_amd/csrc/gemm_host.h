@@ -19,6 +19,8 @@ double kf_gemm_alg_bytes(const OpD &a, const OpD &b, const KfEpilogue &E, long l
 // caller runs the im2col GEMM), -1 error
 int kf_conv_wgrad_halo_try(int M, int N, int K, const OpD &a, const OpD &b, float *dW, long long ldw,
                            float *bias_grad, int accumulate);
+// the weight-gradient halo plan covers the product (no launch)
+bool kf_conv_wgrad_halo_applies(int M, int N, int K, const OpD &a, const OpD &b);
 // kf_halo_debug_last's record (kf_ops.h): what the calling thread's last conv_halo_plan
 // (kind 1) / conv_wgrad_halo_plan (kind 2) chose. v[0] = kind, v[1] = taken, then the
 // fields in kf_ops.h's order. Host only; never read by a launch.

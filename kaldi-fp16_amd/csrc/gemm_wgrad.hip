@@ -241,6 +241,11 @@ extern "C" int kf_gemm_wgrad(int M, int N, int K, const KfOperand *A, const KfOp
                              float *dW, long long ldw, float *bias_grad, int accumulate) {
     return wgrad_impl(M, N, K, A, B, dW, ldw, bias_grad, accumulate, nullptr);
 }
+extern "C" int kf_gemm_wgrad_halo_applies(int M, int N, int K, const KfOperand *A, const KfOperand *B) {
+    OpD a, b;
+    if (!A || !B || !to_dev(*A, a, "A") || !to_dev(*B, b, "B")) return -1;
+    return !b.mk && kf_conv_wgrad_halo_applies(M, N, K, a, b) ? 1 : 0;
+}
 extern "C" int kf_gemm_wgrad_scaled(int M, int N, int K, const KfOperand *A, const KfOperand *B, float *dW,
                                     long long ldw, float *bias_grad, int accumulate, const float *col_scale) {
     if (!col_scale) {

@@ -180,6 +180,22 @@ extern "C" int nnet_set_row_subsampling(KfNet *net, int stride) {
             if (li != first && (net->layers[li].input == net->layers[first].input ||
                                 net->layers[li].input2 == net->layers[first].input))
                 net->conv_c = 0;
+        if (net->conv_c) {
+            // its weight gradient over the compact rows (BackwardPass::conv_wgrad_compact) reads
+            // time-strided rows, which only the 3x3 halo kernel takes, and that kernel does not cover
+            // every geometry (e.g. 64 filters at height 20: the strided halo is too large for its
+            // four waves): such a conv stays on full rows, read gathered. The plan does not depend
+            // on the row count; no launch, so any device pointer serves as the base.
+            const Layer &L = cl.L;
+            const int rows = ((net->max_T - 1) / 3 + 1) * L.hout;
+            KfOperand A = op_im2col(cl, net->dzc, net->max_T, 0);
+            A.tmul = 3;
+            A.nrows = rows;
+            const KfOperand B = op_base(net->dzc, L.fout, rows, L.fout, 0);
+            if (kf_gemm_wgrad_halo_applies &&  // (a weak reference, net_internal.h)
+                kf_gemm_wgrad_halo_applies((int)cl.dt.size() * L.fin, L.fout, rows, &A, &B) != 1)
+                net->conv_c = 0;
+        }
     }
     net->rs_nt = nt;
     net->maxTc = maxTc;
@@ -218,6 +234,8 @@ extern "C" int nnet_debug_backward(KfNet *net, int main_aff, long long stall_cyc
     net->stall_side = stall_cycles;
     return 0;
 }
+
+extern "C" int nnet_debug_alloc_count(const KfNet *net) { return net ? (int)net->allocs.size() : -1; }
 
 extern "C" int nnet_set_wgrad_stream(KfNet *net, int on) {
     if (!net) return -1;

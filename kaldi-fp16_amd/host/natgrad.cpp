@@ -86,6 +86,17 @@ extern "C" int nnet_set_natural_gradient(KfNet *net, const KfNgOpts *opts) {
     net->ng_issued.assign(net->ng_comps.size(), 0);
     net->ng_t = 0;
     net->ng_ran = false;
+    // an earlier call's tables, state and scratch go back first (their sizes follow the options):
+    // every call with options starts from the initial state, and none of them grows the net
+    {
+        void **held[] = {&net->ng_pres_dev, &net->ng_comps_dev, (void **)&net->ng_w32, &net->ng_w16,
+                         (void **)&net->ng_sc, (void **)&net->ng_stat, (void **)&net->ng_report,
+                         &net->ng_apply_scratch, &net->ng_state_scratch, &net->ng_h};
+        for (void **p : held) {
+            net->dfree(*p);
+            *p = nullptr;
+        }
+    }
     if (net->ng_comps.empty()) {
         net->ng_on = true;
         return 0;

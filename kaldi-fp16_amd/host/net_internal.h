@@ -47,6 +47,8 @@ KF_HIDDEN void set_err(const std::string &s);
 #pragma weak kf_bn_train_bwd_apply_rows
 #pragma weak kf_bn_block_stats
 #pragma weak kf_bn_block_bwd_stats
+// (a query: against a backend without it nnet_set_row_subsampling decides as it did before it asked)
+#pragma weak kf_gemm_wgrad_halo_applies
 
 struct ParamRef {
     std::string name;
@@ -230,7 +232,9 @@ struct KfNet {
     // the conv below first_c evaluated on the compact rows only (its output frames 3c and the
     // tail; time-strided halo operand, kf_ops.h KfOperand.tmul): its activation and mask are
     // then in compact rows and first_c reads them directly. Its backward stays on full rows
-    // (the input gradient scattered back). KF_RSUB_CONV=0 at nnet_set_row_subsampling: off.
+    // (the input gradient scattered back). KF_RSUB_CONV=0 at nnet_set_row_subsampling: off; off
+    // too where the halo weight-gradient kernel does not cover the conv's time-strided rows
+    // (kf_ops.h kf_gemm_wgrad_halo_applies).
     int conv_c = 0;
     int rs_nt = 0;                 // tail rows when (T - 1) % 3 != 0
     RowSet rs;                     // the row set of the current forward (rs.Tc == 0: full rows)

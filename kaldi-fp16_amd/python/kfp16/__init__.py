@@ -169,6 +169,7 @@ _sig(nnet, "nnet_set_implicit_dz", _i, _vp, _i)
 _sig(nnet, "nnet_set_row_subsampling", _i, _vp, _i)
 _sig(nnet, "nnet_row_set", _i, _vp, C.POINTER(_i), C.POINTER(_i))
 _sig(nnet, "nnet_debug_backward", _i, _vp, _i, _ll)
+_sig(nnet, "nnet_debug_alloc_count", _i, _vp)
 _sig(core, "kf_debug_spin", _i, _vp, _ll)
 _sig(nnet, "nnet_weights_changed", _i, _vp)
 # per-sequence dropout (kf_nnet.h nnet_set_dropout)
@@ -660,6 +661,10 @@ class Network:
         TDNN-F affine weight gradients run, and a spin of `stall_cycles` GPU cycles on the
         weight-gradient stream before each of its batches of work."""
         check(nnet.nnet_debug_backward(self.h, int(main_aff), int(stall_cycles)), "nnet_debug_backward")
+
+    def debug_alloc_count(self) -> int:
+        """Test hook (kf_nnet.h nnet_debug_alloc_count): the device blocks the net holds now."""
+        return int(nnet.nnet_debug_alloc_count(self.h))
 
     def set_row_subsampling(self, stride: int):
         """Row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): 3 = the layers above

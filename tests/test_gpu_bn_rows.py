@@ -22,6 +22,7 @@ import bn_rows_ref as rr
 import bn_sites_ref as bs
 import bn_train_ref as br
 from conftest import rel_fro
+from history_dev import tiny3_xcfg as _xcfg
 
 pytestmark = pytest.mark.gpu
 
@@ -170,16 +171,6 @@ def test_rows_kernel_argument_checks(gpu):
 # ---------------------------------------------------------------------------
 # network
 # ---------------------------------------------------------------------------
-def _xcfg(dropout=False):
-    from kfp16 import synth
-    x = synth.load_xconfig("tiny.xconfig")
-    old = "name=tdnnf8 dim=256 bottleneck-dim=64 time-stride=1"
-    assert old in x
-    x = x.replace(old, old.replace("time-stride=1", "time-stride=3"))
-    assert x.count("bypass-scale=0.66") == 4
-    return x.replace("bypass-scale=0.66", "bypass-scale=0.66 dropout-proportion=0.0") if dropout else x
-
-
 def _seq(frames):
     return np.asarray([0, 90, 200, frames], np.int32)
 

@@ -60,27 +60,30 @@ def _opts(sw=1.0, xr=XR):
 
 class _Run:
     """One Chain over the case's batch in one layout; run() = compute (+ xent) into fresh
-    sentinel buffers."""
+    sentinel buffers. seqs: the case's sequences this batch is made of (default: all three, in
+    order); chain: a (DenGraph, Chain) to compute with instead of a new pair (it is not closed)."""
 
-    def __init__(self, gpu, c, stride, xs=None):
-        from kfp16 import chain
+    def __init__(self, gpu, c, stride, xs=None, seqs=(0, 1, 2), chain=None):
+        from kfp16 import chain as kc
         self.gpu, self.c, self.stride = gpu, c, stride
-        self.row0, self.rows = cr.layout(FRAMES, stride, compact=stride == 1)
-        self.dg = chain.DenGraph(c.g, c.init)
-        self.ch = chain.Chain(self.dg, max_seqs=3, max_frames=int(FRAMES.max()))
-        self.nb = chain.NumBatch(c.fsts)
-        self.dx = gpu.upload_fp16(cr.place(xs or c.xs, self.row0, stride, self.rows, c.P))
-        self.dy = gpu.upload_fp16(cr.place(c.ys, self.row0, stride, self.rows, c.P, seed=1))
+        self.frames = FRAMES[list(seqs)]
+        self.row0, self.rows = cr.layout(self.frames, stride, compact=stride == 1)
+        self.own = chain is None
+        self.dg = kc.DenGraph(c.g, c.init) if self.own else chain[0]
+        self.ch = kc.Chain(self.dg, max_seqs=3, max_frames=int(FRAMES.max())) if self.own else chain[1]
+        self.nb = kc.NumBatch([c.fsts[i] for i in seqs])
+        self.dx = gpu.upload_fp16(cr.place([(xs or c.xs)[i] for i in seqs], self.row0, stride, self.rows, c.P))
+        self.dy = gpu.upload_fp16(cr.place([c.ys[i] for i in seqs], self.row0, stride, self.rows, c.P, seed=1))
         self.sup = np.zeros(self.rows, bool)
-        for i, T in enumerate(FRAMES):
+        for i in range(len(self.frames)):
             self.sup[self.seq_rows(i)] = True
 
     def seq_rows(self, i):
-        return self.row0[i] + np.arange(FRAMES[i]) * self.stride
+        return self.row0[i] + np.arange(self.frames[i]) * self.stride
 
     def frame_rows(self):
         """row of every (sequence, frame), sequence after sequence: the order of frame_weight"""
-        return np.concatenate([self.seq_rows(i) for i in range(len(FRAMES))])
+        return np.concatenate([self.seq_rows(i) for i in range(len(self.frames))])
 
     def run(self, opts=None, seq_weight=None, frame_weight=None, xent=True, weighted_call=None):
         gpu, c, P = self.gpu, self.c, self.c.P
@@ -89,9 +92,9 @@ class _Run:
         kw = {}
         if weighted_call or seq_weight is not None or frame_weight is not None:
             kw = dict(seq_weight=seq_weight, frame_weight=frame_weight)
-        self.ch.compute(self.nb, self.dx.ptr, P, self.rows, self.row0, FRAMES, self.stride, og.ptr, P, opts, **kw)
+        self.ch.compute(self.nb, self.dx.ptr, P, self.rows, self.row0, self.frames, self.stride, og.ptr, P, opts, **kw)
         out = dict(res=self.ch.result())
-        out["stats"] = self.ch.seq_stats(3).copy()
+        out["stats"] = self.ch.seq_stats(len(self.frames)).copy()
         out["grad"] = gpu.read_fp16(og.ptr, (self.rows, P))
         if xent:
             xg = gpu.upload_fp16(np.full((self.rows, P), cr.SENTINEL, np.float16))
@@ -101,7 +104,7 @@ class _Run:
         return out
 
     def close(self):
-        for h in (self.ch, self.nb, self.dg):
+        for h in (self.ch, self.nb, self.dg) if self.own else (self.nb,):
             h.close()
 
 
