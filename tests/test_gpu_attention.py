@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("cfg,T", [("tiny_att.xconfig", 96), ("tiny_att.xconfig", 301),
-                                   ("cnn_tdnn_17f_att.xconfig", 240)])
+                                   ("cnn_tdnn_17f_att.xconfig", 240),
+                                   ("tiny_att_ctx9.xconfig", 96), ("tiny_att_ctx9.xconfig", 50)])
 def test_attention_network_forward_backward(gpu, cfg, T):
     kf = gpu
     from kfp16 import synth
@@ -32,7 +33,7 @@ def test_attention_network_forward_backward(gpu, cfg, T):
     on = _oracle(xcfg, params, bns, feats)
     on.forward(feats.astype(np.float32), force_masks=masks)
     P = [dout for name, ty, din, dout in net.layers if name == "output"][0]
-    if cfg == "tiny_att.xconfig":
+    if cfg.startswith("tiny_att"):   # the tiny configs (ctx9: the host's att_args on 2 / 6 / 1)
         og = (np.random.default_rng(7).standard_normal((T, P)) * 0.05).astype(np.float16)
         gbuf = kf.upload_fp16(og)
         net.backward(gbuf.ptr)
@@ -77,6 +78,26 @@ def test_attention_network_forward_backward(gpu, cfg, T):
     gm = float(np.exp(np.mean(logs)))
     assert not bad, "grad errors vs fp32 (gpu, F): " + ", ".join(f"{k}={a:.2e}/{b:.2e}" for k, (a, b) in bad.items())
     assert gm <= 1.15, f"GPU gradients noisier than the fp16 restatement: geometric-mean error ratio {gm:.3f}"
+
+
+def test_attention_context_65_is_refused(gpu):
+    """A device network whose attention context is 65 (40 left, 24 right) is refused at
+    construction; every other dim of the layer is one the device accepts (affine 8 x 96 = 768,
+    output 8 x 80 = 640), so the context alone is the reason. With context 64 it builds."""
+    kf = gpu
+    from kfp16 import synth
+    lines = synth.load_xconfig("tiny_att.xconfig").splitlines()
+    att = [i for i, l in enumerate(lines) if l.startswith("attention-relu-batchnorm-layer")][0]
+    lines[att + 1] = lines[att + 1].replace("dim=160", "dim=640")
+
+    def xcfg(nr):
+        lines[att] = ("attention-relu-batchnorm-layer name=attention3 num-heads=8 value-dim=15 key-dim=8 "
+                      f"num-left-inputs=40 num-right-inputs={nr} time-stride=1")
+        return "\n".join(lines) + "\n"
+
+    with pytest.raises(kf.KfError, match="context <= 64"):
+        kf.Network(xcfg(24), max_frames=96)
+    kf.Network(xcfg(23).replace("value-dim=15", "value-dim=16"), max_frames=96).close()
 
 
 def test_attention_import_key_scale(gpu):

@@ -21,6 +21,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from attention_ref import att_backward
 from conftest import rel_fro
 
 pytestmark = pytest.mark.gpu
@@ -30,37 +31,6 @@ class KfAttention(C.Structure):
     _fields_ = [("proj", C.c_void_p), ("ldp", C.c_longlong), ("T", C.c_int), ("num_heads", C.c_int),
                 ("key_dim", C.c_int), ("value_dim", C.c_int), ("context", C.c_int), ("num_left", C.c_int),
                 ("stride", C.c_int), ("key_scale", C.c_float)]
-
-
-def att_backward(proj, dz, H, kd, vd, nl, nr, st, s, dt):
-    """The exact gradient of the restricted attention (the kernel header's formulas) in
-    dtype dt, in the oracle's loop order per (t, h)."""
-    T = proj.shape[0]
-    ctx, A, od = 1 + nl + nr, 2 * kd + vd + 1 + nl + nr, vd + 1 + nl + nr
-    P = proj.astype(dt).reshape(T, H, A)
-    G = dz.astype(dt).reshape(T, H, od)
-    dP = np.zeros_like(P)
-    rows = np.arange(T)[:, None] + (np.arange(ctx)[None, :] - nl) * st          # [T, ctx]
-    live = (rows >= 0) & (rows < T)
-    rc = np.clip(rows, 0, T - 1)
-    for h in range(H):
-        key, val = P[:, h, :kd], P[:, h, kd:kd + vd]
-        qk, qc = P[:, h, kd + vd:2 * kd + vd], P[:, h, 2 * kd + vd:]
-        b = qc + dt(s) * np.where(live, np.einsum("td,tod->to", qk, key[rc]), dt(0))
-        e = np.exp((b - b.max(1, keepdims=True)).astype(np.float64)).astype(dt)
-        w = e / e.sum(1, keepdims=True, dtype=dt)
-        gv, gw = G[:, h, :vd], G[:, h, vd:]
-        dw = gw + np.where(live, np.einsum("td,tod->to", gv, val[rc]), dt(0))
-        sw = (w * dw).sum(1, keepdims=True, dtype=dt)
-        db = w * (dw - sw)
-        dP[:, h, 2 * kd + vd:] = db
-        dbl = np.where(live, db, dt(0))
-        dP[:, h, kd + vd:2 * kd + vd] = dt(s) * np.einsum("to,tod->td", dbl, key[rc])
-        for o in range(ctx):  # scatter to the attended rows
-            ok = live[:, o]
-            np.add.at(dP[:, h, :kd], rc[ok, o], dt(s) * dbl[ok, o, None] * qk[ok])
-            np.add.at(dP[:, h, kd:kd + vd], rc[ok, o], w[ok, o, None] * gv[ok])
-    return dP.reshape(T, H * A)
 
 
 @pytest.mark.parametrize("H,kd,vd,T,seed", [(8, 64, 128, 240, 7), (8, 64, 128, 240, 8), (4, 16, 32, 301, 3)])
