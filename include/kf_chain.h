@@ -160,6 +160,16 @@ int kf_chain_xent(KfChain *c, const KfNumBatch *num, const KfChainOpts *opts,
  * may be NULL. -1 when no kf_chain_xent ran since the last kf_chain_compute. */
 int kf_chain_xent_result(KfChain *c, double *xent_objf, double *total_weight);
 
+/* The loss scale of the fp16 train step (kf_ops.h kf_loss_scale_*). scale_dev: one
+ * float in device memory (kf_nnet.h nnet_loss_scale_ptr), read by the kernels when they run, so
+ * its writer only has to be ahead of them on the stream; NULL: off, the launches are what they
+ * were. While it is set, kf_chain_compute, kf_chain_compute_weighted and kf_chain_xent multiply
+ * the finished fp32 derivative of an element by *scale_dev (with a frame weight f: by
+ * f * *scale_dev) before its one rounding to fp16, which overflows to inf like every fp16 store
+ * of the backward. No statistic, objective value or KfChainResult field depends on it; with
+ * 1.0f there every output is bit-identical to off. The memory must outlive the calls. */
+void kf_chain_set_grad_scale(KfChain *c, const float *scale_dev);
+
 /* diagnostics: phase timestamps of the den forward kernel (sequence 0, block 0,
  * frames 16..47, 8 u64 each, 100 MHz wall clock), then the arc-phase end of every wave
  * of blocks 0 and 1 (32 x 2 x 16 u64) into a device buffer; NULL = off */

@@ -144,6 +144,33 @@ int nnet_update(KfNet *net, float lr, float momentum, float max_param_change, fl
  * global norm N and scale S. */
 int nnet_update_stats(KfNet *net, float *norms, float *scales, int n, float *global_norm, float *global_scale);
 
+/* Dynamic loss scaling of the fp16 train step, kept on the device (kf_ops.h kf_loss_scale_*,
+ * DESIGN.md §30). The objective multiplies its derivative by the scale (hand
+ * nnet_loss_scale_ptr to kf_chain.h kf_chain_set_grad_scale); nnet_backward is linear in its
+ * seeds, so the gradient buffer then holds scale * G (after a data-parallel all-reduce: the
+ * mean of the ranks' scaled gradients, an inf reaching every rank). While the mode is on, nnet_sgd
+ * and nnet_update first check every trainable element of the gradient buffer (the update's
+ * segment table; the alignment padding between tensors is not read) for a non-finite value and
+ * advance the state, then run the update with the state: on an overflow the step is skipped
+ * (master, fp16 weights and velocity keep their bits, the scale is multiplied by backoff, and a
+ * skipped nnet_update reports all-zero stats), else the update reads g / scale. No host
+ * synchronisation per step and no allocation after the set call.
+ *   nnet_set_loss_scale        opts NULL: off, nnet_sgd / nnet_update are the plain calls. Else the
+ *                              state is allocated (once per net) and initialised from opts. Refused
+ *                              beside natural gradient (its Fisher state is not scale-equivariant
+ *                              across a change of the scale) and MXFP8 mode (block scales of its own),
+ *                              in either order.
+ *   nnet_loss_scale_ptr        the device float holding the scale, NULL while off
+ *   nnet_set_loss_scale_value  the scale (clamped to [min_scale, max_scale]), since = 0: a
+ *                              checkpoint restore, tests
+ *   nnet_loss_scale_stats      synchronises; any out pointer may be NULL. steps / skipped count the
+ *                              updates since nnet_set_loss_scale, last_overflow is the last check's. */
+int nnet_set_loss_scale(KfNet *net, const KfLossScaleOpts *opts);
+const float *nnet_loss_scale_ptr(const KfNet *net);
+int nnet_set_loss_scale_value(KfNet *net, float scale);
+int nnet_loss_scale_stats(KfNet *net, float *scale, int *since, long long *steps, long long *skipped,
+                          int *last_overflow);
+
 /* Semi-orthogonal constraint (kf_ops.h kf_orthonormal_constrain): Kaldi's
  * ConstrainOrthonormal, which keeps a TDNN-F bottleneck matrix and the prefinal layers' small
  * projection close to semi-orthogonal. Every update component whose tensor is one weight

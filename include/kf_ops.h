@@ -293,6 +293,57 @@ int kf_update_maxchange(float *w32, void *w16, const float *g, float *v, long lo
                         float lr, float momentum, float max_param_change, float l2_scale,
                         void *scratch, float *stats);
 
+/* ---- Dynamic loss scaling, kept on the device (csrc/loss_scale.hip) ----
+ * The objective multiplies its derivative by `scale` before the one rounding to fp16
+ * (kf_chain.h kf_chain_set_grad_scale); the backward is linear in the gradient, so the fp32
+ * gradient buffer then holds scale * G. The update checks every trainable element of it for
+ * a non-finite value, skips the step on one and unscales by 1 / scale otherwise. The rule is
+ * kaldi_loss_scaler_update's (kaldi_bridge.h), per step, with `overflow` the check's answer:
+ *   inv_used = 1 / scale                       (the scale this step's objective read)
+ *   overflow:  skip = 1, scale = max(min_scale, scale * backoff), since = 0
+ *   else:      skip = 0, ++since; since >= growth_interval: scale = min(max_scale, scale * growth), since = 0
+ * The state is one block of device memory of kf_loss_scale_state_bytes() bytes, 16-byte
+ * aligned, whose first float is the scale (the pointer kf_chain_set_grad_scale takes); the
+ * options live in it. No host round trip, no atomics: the decision, the state and the skipped
+ * step stay on the current stream.
+ *   kf_loss_scale_init       state <- opts, scale = init_scale clamped to [min_scale, max_scale],
+ *                            counters zero (one small launch); -1 on bad options
+ *   kf_loss_scale_set_scale  scale <- value (clamped), since = 0 (a checkpoint restore, tests)
+ *   kf_loss_scale_check      over the segments of a kf_update_maxchange table (comps are not read;
+ *                            ncomp bounds a segment's comp), cut into the same KF_UPD_CHUNK chunks:
+ *                            one flag per workgroup into scratch (kf_loss_scale_scratch_bytes(n, nseg)
+ *                            bytes, 4-byte aligned), then one workgroup folds the flags and advances
+ *                            the state by the rule above. What no segment covers is not read. Two launches.
+ *   kf_loss_scale_read       synchronises the current stream; any pointer may be NULL
+ *   kf_update_maxchange_scaled / kf_sgd_flat_scaled
+ *                            the update calls with the state: every kernel loads skip and inv_used
+ *                            block-uniformly, returns before it has written a byte on skip, and
+ *                            uses g * inv_used otherwise. A skipped kf_update_maxchange_scaled
+ *                            reports stats all zero (n_c = 0, s_c = 0, N = 0, S = 0: the norms are
+ *                            not computed). state NULL: the plain call, launch for launch.
+ * With a power of two as the scale g * inv_used is exact, and the update is bit-identical to
+ * the plain one on the unscaled gradient. */
+typedef struct KfLossScaleOpts {
+    float init_scale, growth, backoff; /* 65536, 2, 0.5 */
+    int growth_interval;               /* 2000 */
+    float min_scale, max_scale;        /* 1, 65536 */
+} KfLossScaleOpts;
+void kf_loss_scale_default_opts(KfLossScaleOpts *opts);
+long long kf_loss_scale_state_bytes(void);
+long long kf_loss_scale_scratch_bytes(long long n, int nseg);
+int kf_loss_scale_init(void *state, const KfLossScaleOpts *opts);
+int kf_loss_scale_set_scale(void *state, float scale);
+int kf_loss_scale_check(void *state, const float *g, long long n, const KfUpdSegment *segments, int nseg,
+                        int ncomp, void *scratch);
+int kf_loss_scale_read(const void *state, float *scale, int *since, long long *steps, long long *skipped,
+                       int *last_overflow);
+int kf_update_maxchange_scaled(float *w32, void *w16, const float *g, float *v, long long n,
+                               const KfUpdSegment *segments, int nseg, const KfUpdComp *comps, int ncomp,
+                               float lr, float momentum, float max_param_change, float l2_scale,
+                               void *scratch, float *stats, const void *loss_scale_state);
+int kf_sgd_flat_scaled(float *w32, void *w16, const float *g, float *v, float lr, float mom,
+                       long long n, const void *loss_scale_state);
+
 /* ---- Semi-orthogonal constraint (csrc/orthonormal.hip) ----
  * Kaldi's ConstrainOrthonormal over every constrained matrix of a flat parameter set in one
  * call. A matrix is W [K rows x n cols] (y = x W, the transpose of Kaldi's M: the columns

@@ -102,7 +102,8 @@ struct KfChain {
     // used (kf_chain_xent uses the same)
     float *d_seq_w = nullptr, *d_frame_w = nullptr;
     bool use_seq_w = false, use_frame_w = false;
-    ChainLayoutKey last;          // cache of the last run's layout
+    const float *grad_scale = nullptr;  // kf_chain_set_grad_scale: caller-owned device float, or off
+    ChainLayoutKey last;         // cache of the last run's layout
     // pinned staging of the layout upload: two slots, each reused after its copy's event
     char *h_stage[2] = {nullptr, nullptr};
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
@@ -565,6 +566,7 @@ static bool launch_denominator(KfChain *c, const KfChainOpts *opts, const void *
     r.opts = *opts;
     r.seq_w = c->use_seq_w ? c->d_seq_w : nullptr;
     r.frame_w = c->use_frame_w ? c->d_frame_w : nullptr;
+    r.grad_scale = c->grad_scale;
     // algorithmic bytes: per frame three streamed passes over the
     // packed arc records, alpha' stored and re-read, the output row read twice
     // and the gradient row written once
@@ -679,6 +681,7 @@ extern "C" int kf_chain_xent(KfChain *c, const KfNumBatch *num, const KfChainOpt
     r.xr = opts->xent_regularize;
     r.seq_w = c->use_seq_w ? c->d_seq_w : nullptr;
     r.frame_w = c->use_frame_w ? c->d_frame_w : nullptr;
+    r.grad_scale = c->grad_scale;
     double frames = 0;
     for (int f : c->last.frames) {
         frames += f;
@@ -691,6 +694,10 @@ extern "C" int kf_chain_xent(KfChain *c, const KfNumBatch *num, const KfChainOpt
     }
     c->xent_ran = true;
     return 0;
+}
+
+extern "C" void kf_chain_set_grad_scale(KfChain *c, const float *scale_dev) {
+    if (c) c->grad_scale = scale_dev;
 }
 
 // Synchronises; the per-frame terms of every sequence summed in double, frame by frame and

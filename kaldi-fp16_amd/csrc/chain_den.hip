@@ -871,7 +871,9 @@ __global__ __launch_bounds__(DEN_THREADS) void k_den_post(const DenDev g, const 
                 const bool even = (tf & 1) == 0;
                 // the frame's deriv weight, one block-uniform load (Kaldi's MulRowsVec, after
                 // every term is in): one fp32 multiply, then the one rounding
-                const float fw = r.frame_w ? r.frame_w[(size_t)seq * r.max_frames + tf] : 1.0f;
+                // (the loss scale, DESIGN §30: one more block-uniform load beside it)
+                float fw = r.frame_w ? r.frame_w[(size_t)seq * r.max_frames + tf] : 1.0f;
+                if (r.grad_scale) fw *= *r.grad_scale;
                 for (int pdf = tid; pdf < P; pdf += DEN_THREADS) {
                     const float x = (float)xrow[pdf];
                     float d = 0.0f;

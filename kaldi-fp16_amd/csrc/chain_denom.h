@@ -63,6 +63,9 @@ struct DenRun {
     // kf_chain_compute_weighted, null = ones
     const float *seq_w;     // [nseq] the example's weight (times opts.supervision_weight)
     const float *frame_w;   // [nseq][max_frames] deriv weight of (sequence, frame)
+    // kf_chain_set_grad_scale, null = 1: one device float, the factor on the finished
+    // derivative row before its one rounding to fp16
+    const float *grad_scale;
 };
 
 enum { DEN_ABI = 0, DEN_PRODUCT = 1 };

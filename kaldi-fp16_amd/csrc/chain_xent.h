@@ -26,6 +26,7 @@ struct XentRun {
     float xr;                // xent_regularize: with seq_w, scale = xr * (w * seq_w[i])
     const float *seq_w;      // [nseq]
     const float *frame_w;    // [nseq][part_ld]
+    const float *grad_scale; // kf_chain_set_grad_scale, null = 1: one device float
 };
 
 // total_frames = all supervised frames (the profile record's bytes)

@@ -68,7 +68,9 @@ __global__ __launch_bounds__(XENT_THREADS) void k_chain_xent(const XentRun r) {
         w = r.w * r.seq_w[seq];
         scale = r.xr * w;
     }
-    const float fw = r.frame_w ? r.frame_w[(size_t)seq * r.part_ld + t] : 1.0f;
+    // (the loss scale, DESIGN §30: one more block-uniform load beside the frame weight)
+    float fw = r.frame_w ? r.frame_w[(size_t)seq * r.part_ld + t] : 1.0f;
+    if (r.grad_scale) fw *= *r.grad_scale;
     const bool zero = !(scale != 0.0f);
     float ob = 0.f;
     for (int c0 = 0; c0 < P; c0 += XENT_CHUNK) {

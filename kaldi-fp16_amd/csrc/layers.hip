@@ -9,6 +9,7 @@
 // All are HBM-bound; every lane moves 16-byte vectors.
 #include "kf_common.h"
 #include "../../include/kf_ops.h"
+#include "loss_scale_state.h"
 
 KF_DECLARE_ERR(lay)
 
@@ -230,9 +231,21 @@ __global__ void k_conv_c1_reduce(const float *slab, int nblk, int n, float *dW, 
     }
 }
 
-// flat SGD with momentum and fp32 master weights; fp32 gradient
-__global__ void k_sgd_flat(float *w32, h16 *w16, const float *g, float *v, float lr, float mom,
-                           long long n) {
+// flat SGD with momentum and fp32 master weights; fp32 gradient. LS (kf_sgd_flat_scaled, DESIGN
+// §30): the gradient is g * inv, the product kept out of any contraction with what follows, so
+// the rest is the plain kernel's arithmetic.
+template <bool LS>
+__device__ __forceinline__ float sgd_grad(float g, float inv) {
+    if constexpr (LS) {
+        float r = g * inv;
+        asm volatile("" : "+v"(r));
+        return r;
+    }
+    return g;
+}
+template <bool LS>
+__device__ __forceinline__ void sgd_flat_body(float *w32, h16 *w16, const float *g, float *v, float lr, float mom,
+                                              long long n, float inv) {
     const long long n4 = n / 4;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
          i += (long long)gridDim.x * blockDim.x) {
@@ -242,7 +255,7 @@ __global__ void k_sgd_flat(float *w32, h16 *w16, const float *g, float *v, float
         half4 hv;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            vv[e] = mom * vv[e] + gv[e];
+            vv[e] = mom * vv[e] + sgd_grad<LS>(gv[e], inv);
             wv[e] = wv[e] - lr * vv[e];
             hv[e] = f2h(wv[e]);
         }
@@ -252,7 +265,7 @@ __global__ void k_sgd_flat(float *w32, h16 *w16, const float *g, float *v, float
     }
     for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
-        const float vv = mom * v[i] + g[i];
+        const float vv = mom * v[i] + sgd_grad<LS>(g[i], inv);
         v[i] = vv;
         // w16 = rne(the stored fp32 w), as the vector body: without the barrier hipcc folds the
         // update into v_fma_mixlo_f16, which rounds the exact w - lr*v to fp16 once and differs
@@ -262,6 +275,16 @@ __global__ void k_sgd_flat(float *w32, h16 *w16, const float *g, float *v, float
         w32[i] = w;
         w16[i] = f2h(w);
     }
+}
+__global__ void k_sgd_flat(float *w32, h16 *w16, const float *g, float *v, float lr, float mom,
+                           long long n) {
+    sgd_flat_body<false>(w32, w16, g, v, lr, mom, n, 1.f);
+}
+// with the loss scale's state: skip and inv_used are block-uniform loads; on skip no byte is written
+__global__ void k_sgd_flat_scaled(float *w32, h16 *w16, const float *g, float *v, float lr, float mom,
+                                  long long n, const KfLossScaleState *ls) {
+    if (ls->skip) return;
+    sgd_flat_body<true>(w32, w16, g, v, lr, mom, n, ls->inv_used);
 }
 
 // fp16 <- fp32 for a flat parameter set (master -> working copy)
@@ -498,6 +521,16 @@ int kf_sgd_flat(float *w32, void *w16, const float *g, float *v, float lr, float
     k_sgd_flat<<<kf_blocks(n / 4 + 1, 256, 8192), 256, 0, kf_stream()>>>(w32, (h16 *)w16, g, v, lr,
                                                                         mom, n);
     return lay_check("sgd_flat");
+}
+
+int kf_sgd_flat_scaled(float *w32, void *w16, const float *g, float *v, float lr, float mom,
+                       long long n, const void *loss_scale_state) {
+    if (!loss_scale_state) return kf_sgd_flat(w32, w16, g, v, lr, mom, n);
+    kf_take_pending(__func__);
+    if (n <= 0) return 0;
+    k_sgd_flat_scaled<<<kf_blocks(n / 4 + 1, 256, 8192), 256, 0, kf_stream()>>>(
+        w32, (h16 *)w16, g, v, lr, mom, n, (const KfLossScaleState *)loss_scale_state);
+    return lay_check("sgd_flat_scaled");
 }
 
 int kf_f32_to_f16_flat(const float *src, void *dst, long long n) {

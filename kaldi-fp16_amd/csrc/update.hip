@@ -14,48 +14,18 @@
 // Every sum runs in a fixed order (per thread in address order, the wave by shuffles, the
 // waves through LDS in wave order, the workgroups' partials lane-strided in double and the
 // same shuffle tree), so two runs on the same inputs give the same bits.
-#include "kf_common.h"
-#include "../../include/kf_ops.h"
+//
+// kf_update_maxchange_scaled is the same three launches with the dynamic loss
+// scale's state: each kernel's LS instantiation loads skip and inv_used block-uniformly, returns
+// before it has written a byte on skip and reads g * inv_used otherwise. The plain call runs the
+// LS = false instantiations, which are the kernels as they were.
+#include "upd_chunk.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kScaleThreads = 1024;  // k_upd_scales: 16 waves, each a component at a time
 static_assert(KF_UPD_CHUNK % (4 * kThreads) == 0, "a chunk is whole float4 rounds of the workgroup");
-
-// the chunk of workgroup b: elements [cb, ce) of component comp; false when b is past the table
-__device__ __forceinline__ bool upd_chunk(const KfUpdSegment *segs, int nseg, int ncomp, long long n, int b,
-                                          long long &cb, long long &ce, int &comp) {
-    int lo = 0, hi = nseg;  // the first segment whose first_wg lies above b
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (segs[mid].first_wg > b) hi = mid;
-        else lo = mid + 1;
-    }
-    if (lo == 0) return false;
-    const KfUpdSegment s = segs[lo - 1];
-    // a table that does not fit the buffer addresses nothing outside [0, n)
-    const long long sb = s.begin < 0 ? 0 : s.begin, se = s.end > n ? n : s.end;
-    cb = sb + (long long)(b - s.first_wg) * KF_UPD_CHUNK;
-    if (cb >= se) return false;
-    ce = cb + KF_UPD_CHUNK < se ? cb + KF_UPD_CHUNK : se;
-    comp = s.comp;
-    return comp >= 0 && comp < ncomp;
-}
-
-// [cb, ce) = scalar head [cb, a0), float4 body [a0, a1), scalar tail [a1, ce); a0 % 4 == 0
-__device__ __forceinline__ void upd_split(long long cb, long long ce, long long &a0, long long &a1) {
-    a0 = (cb + 3) & ~3ll;
-    if (a0 > ce) a0 = ce;
-    a1 = a0 + ((ce - a0) & ~3ll);
-}
-// the (at most six) scalar elements of a chunk, one per thread: index or -1
-__device__ __forceinline__ long long upd_scalar(long long cb, long long ce, long long a0, long long a1, int t) {
-    const long long nh = a0 - cb;
-    if (t < nh) return cb + t;
-    const long long i = a1 + (t - nh);
-    return i < ce ? i : -1;
-}
 
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
@@ -74,11 +44,26 @@ __device__ __forceinline__ float upd_velocity(float mom, float v, float g, doubl
     return (float)((double)mom * (double)v + (double)g + l2s * (double)w);
 }
 
+// the gradient a scaled update reads: g / (the scale it was made with). The barrier keeps the
+// product out of any contraction with what follows, so the rest is the plain kernel's arithmetic
+__device__ __forceinline__ float upd_unscale(float g, float inv) {
+    float r = g * inv;
+    asm volatile("" : "+v"(r));
+    return r;
+}
+
+template <bool LS>
 __global__ __launch_bounds__(kThreads) void k_upd_velocity(const float *__restrict__ w32, const float *__restrict__ g,
                                                            float *__restrict__ v, long long n,
                                                            const KfUpdSegment *__restrict__ segs, int nseg,
                                                            const KfUpdComp *__restrict__ comps, int ncomp, float lr, float mom,
-                                                           float l2_scale, float *__restrict__ partial) {
+                                                           float l2_scale, float *__restrict__ partial,
+                                                           const KfLossScaleState *__restrict__ ls) {
+    float inv = 1.f;
+    if constexpr (LS) {
+        if (ls->skip) return;  // block-uniform: nothing of v is written
+        inv = ls->inv_used;
+    }
     long long cb, ce, a0, a1;
     int c;
     if (!upd_chunk(segs, nseg, ncomp, n, blockIdx.x, cb, ce, c)) return;  // the same in every thread
@@ -89,12 +74,13 @@ __global__ __launch_bounds__(kThreads) void k_upd_velocity(const float *__restri
     upd_split(cb, ce, a0, a1);
     float acc = 0.f;
     for (long long i = a0 + 4 * threadIdx.x; i < a1; i += 4 * kThreads) {
-        const float4v gv = *reinterpret_cast<const float4v *>(g + i);
+        float4v gv = *reinterpret_cast<const float4v *>(g + i);
         float4v vv = *reinterpret_cast<const float4v *>(v + i);
         float4v wv = {0.f, 0.f, 0.f, 0.f};
         if (l2on) wv = *reinterpret_cast<const float4v *>(w32 + i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
+            if constexpr (LS) gv[e] = upd_unscale(gv[e], inv);
             vv[e] = upd_velocity(mom, vv[e], gv[e], l2s, wv[e]);
             const float d = dl * vv[e];
             acc += d * d;
@@ -103,7 +89,8 @@ __global__ __launch_bounds__(kThreads) void k_upd_velocity(const float *__restri
     }
     const long long i = upd_scalar(cb, ce, a0, a1, threadIdx.x);
     if (i >= 0) {
-        const float vn = upd_velocity(mom, v[i], g[i], l2s, l2on ? w32[i] : 0.f);
+        const float gi = LS ? upd_unscale(g[i], inv) : g[i];
+        const float vn = upd_velocity(mom, v[i], gi, l2s, l2on ? w32[i] : 0.f);
         v[i] = vn;
         const float d = dl * vn;
         acc += d * d;
@@ -124,10 +111,20 @@ __global__ __launch_bounds__(kThreads) void k_upd_velocity(const float *__restri
 // workgroup partials lane-strided in double, then the shuffle tree. n_c, s_c -> stats,
 // (s_c n_c)^2 -> clip2; then wave 0 sums clip2 the same way for N and S, and every thread
 // writes step[c] = S * s_c * lr * lrf_c, the factor k_upd_apply multiplies v by.
+// LS, on skip: the partials were not written; the report is all zero (n_c, s_c, N, S) and so is step.
+template <bool LS>
 __global__ __launch_bounds__(kScaleThreads) void k_upd_scales(const KfUpdComp *__restrict__ comps, int ncomp,
                                                          const float *__restrict__ partial, int npartial, float lr,
                                                          float max_param_change, double *__restrict__ clip2,
-                                                         float *__restrict__ step, float *__restrict__ stats) {
+                                                         float *__restrict__ step, float *__restrict__ stats,
+                                                         const KfLossScaleState *__restrict__ ls) {
+    if constexpr (LS) {
+        if (ls->skip) {
+            for (int i = threadIdx.x; i < 2 * ncomp + 2; i += kScaleThreads) stats[i] = 0.f;
+            for (int c = threadIdx.x; c < ncomp; c += kScaleThreads) step[c] = 0.f;
+            return;
+        }
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int c = wave; c < ncomp; c += kScaleThreads / 64) {
         const KfUpdComp cp = comps[c];
@@ -174,10 +171,15 @@ __device__ __forceinline__ float upd_weight(float w, float f, float v) {
     return r;
 }
 
+template <bool LS>
 __global__ __launch_bounds__(kThreads) void k_upd_apply(float *__restrict__ w32, h16 *__restrict__ w16,
                                                         const float *__restrict__ v, long long n,
                                                         const KfUpdSegment *__restrict__ segs, int nseg, int ncomp,
-                                                        const float *__restrict__ step) {
+                                                        const float *__restrict__ step,
+                                                        const KfLossScaleState *__restrict__ ls) {
+    if constexpr (LS) {
+        if (ls->skip) return;  // block-uniform: nothing of w32 / w16 is written
+    }
     long long cb, ce, a0, a1;
     int c;
     if (!upd_chunk(segs, nseg, ncomp, n, blockIdx.x, cb, ce, c)) return;
@@ -203,8 +205,6 @@ __global__ __launch_bounds__(kThreads) void k_upd_apply(float *__restrict__ w32,
     }
 }
 
-// workgroups launched: at least one per chunk of any segment table over [0, n)
-long long upd_grid(long long n, int nseg) { return n / KF_UPD_CHUNK + nseg; }
 size_t upd_align(size_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace
@@ -215,31 +215,59 @@ extern "C" long long kf_update_scratch_bytes(long long n, int nseg, int ncomp) {
                        upd_align((size_t)ncomp * 4));
 }
 
-extern "C" int kf_update_maxchange(float *w32, void *w16, const float *g, float *v, long long n,
-                                   const KfUpdSegment *segments, int nseg, const KfUpdComp *comps, int ncomp, float lr,
-                                   float momentum, float max_param_change, float l2_scale, void *scratch,
-                                   float *stats) {
-    kf_take_pending(__func__);
+static int update_maxchange(const char *fn, float *w32, void *w16, const float *g, float *v, long long n,
+                            const KfUpdSegment *segments, int nseg, const KfUpdComp *comps, int ncomp, float lr,
+                            float momentum, float max_param_change, float l2_scale, void *scratch, float *stats,
+                            const KfLossScaleState *ls) {
+    kf_take_pending(fn);
     if (n < 0 || nseg < 0 || ncomp < 0 || !(max_param_change >= 0.f)) {
-        kf_report_error("kf_update_maxchange: bad arguments (n %lld, %d segments, %d components, max_param_change %g)",
-                        n, nseg, ncomp, (double)max_param_change);
+        kf_report_error("%s: bad arguments (n %lld, %d segments, %d components, max_param_change %g)", fn, n, nseg, ncomp,
+                        (double)max_param_change);
         return -1;
     }
     if (n == 0 || nseg == 0 || ncomp == 0) return 0;
     const long long grid = upd_grid(n, nseg);
     if (!w32 || !w16 || !g || !v || !segments || !comps || !scratch || !stats || grid > 0x7fffffffll ||
-        ((uintptr_t)w32 | (uintptr_t)g | (uintptr_t)v) % 16 || (uintptr_t)w16 % 8 || (uintptr_t)scratch % 8) {
-        kf_report_error("kf_update_maxchange: null or misaligned buffer (w32 / g / v 16 bytes, w16 and scratch 8), or "
-                        "more than 2^31 workgroups");
+        ((uintptr_t)w32 | (uintptr_t)g | (uintptr_t)v) % 16 || (uintptr_t)w16 % 8 || (uintptr_t)scratch % 8 ||
+        (uintptr_t)ls % 8) {
+        kf_report_error("%s: null or misaligned buffer (w32 / g / v 16 bytes, w16 and scratch 8), or "
+                        "more than 2^31 workgroups", fn);
         return -1;
     }
     float *partial = (float *)scratch;
     double *clip2 = (double *)((char *)scratch + upd_align((size_t)grid * 4));
     float *step = (float *)((char *)clip2 + upd_align((size_t)ncomp * 8));
-    k_upd_velocity<<<(unsigned)grid, kThreads, 0, kf_stream()>>>(w32, g, v, n, segments, nseg, comps, ncomp, lr, momentum,
-                                                                  l2_scale, partial);
-    k_upd_scales<<<1, kScaleThreads, 0, kf_stream()>>>(comps, ncomp, partial, (int)grid, lr, max_param_change, clip2, step,
-                                                  stats);
-    k_upd_apply<<<(unsigned)grid, kThreads, 0, kf_stream()>>>(w32, (h16 *)w16, v, n, segments, nseg, ncomp, step);
-    return hipGetLastError() == hipSuccess ? 0 : (kf_report_error("kf_update_maxchange: launch failed"), -1);
+    hipStream_t st = kf_stream();
+    if (ls) {
+        k_upd_velocity<true><<<(unsigned)grid, kThreads, 0, st>>>(w32, g, v, n, segments, nseg, comps, ncomp, lr, momentum,
+                                                                  l2_scale, partial, ls);
+        k_upd_scales<true><<<1, kScaleThreads, 0, st>>>(comps, ncomp, partial, (int)grid, lr, max_param_change, clip2, step,
+                                                        stats, ls);
+        k_upd_apply<true><<<(unsigned)grid, kThreads, 0, st>>>(w32, (h16 *)w16, v, n, segments, nseg, ncomp, step, ls);
+    } else {
+        k_upd_velocity<false><<<(unsigned)grid, kThreads, 0, st>>>(w32, g, v, n, segments, nseg, comps, ncomp, lr, momentum,
+                                                                   l2_scale, partial, nullptr);
+        k_upd_scales<false><<<1, kScaleThreads, 0, st>>>(comps, ncomp, partial, (int)grid, lr, max_param_change, clip2, step,
+                                                         stats, nullptr);
+        k_upd_apply<false><<<(unsigned)grid, kThreads, 0, st>>>(w32, (h16 *)w16, v, n, segments, nseg, ncomp, step, nullptr);
+    }
+    if (hipGetLastError() == hipSuccess) return 0;
+    kf_report_error("%s: launch failed", fn);
+    return -1;
+}
+
+extern "C" int kf_update_maxchange(float *w32, void *w16, const float *g, float *v, long long n,
+                                   const KfUpdSegment *segments, int nseg, const KfUpdComp *comps, int ncomp, float lr,
+                                   float momentum, float max_param_change, float l2_scale, void *scratch,
+                                   float *stats) {
+    return update_maxchange(__func__, w32, w16, g, v, n, segments, nseg, comps, ncomp, lr, momentum, max_param_change,
+                            l2_scale, scratch, stats, nullptr);
+}
+
+extern "C" int kf_update_maxchange_scaled(float *w32, void *w16, const float *g, float *v, long long n,
+                                          const KfUpdSegment *segments, int nseg, const KfUpdComp *comps, int ncomp,
+                                          float lr, float momentum, float max_param_change, float l2_scale,
+                                          void *scratch, float *stats, const void *loss_scale_state) {
+    return update_maxchange(__func__, w32, w16, g, v, n, segments, nseg, comps, ncomp, lr, momentum, max_param_change,
+                            l2_scale, scratch, stats, (const KfLossScaleState *)loss_scale_state);
 }

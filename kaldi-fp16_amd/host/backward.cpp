@@ -1311,6 +1311,7 @@ extern "C" const void *nnet_debug_tensor(KfNet *net, const char *what, int layer
         if (w == "g" + std::to_string(i)) return net->g[i];
     }
     if (w == "dbott") return net->dbott_last ? net->dbott_last : net->dbott;
+    if (w == "vel") return net->vel;  // the updates' velocity, fp32 [num_params]
     // the MXFP8 copies of dz[layer] (layer = buffer 0 / 1) and the layer whose affine input
     // gradient reads it (as an int, through the pointer's low bits: -1 none), MXFP8 train step
     if ((w == "dz8q" || w == "dz8s" || w == "dz8layer") && layer >= 0 && layer <= 2) {

@@ -25,6 +25,7 @@ bool mode_on(const KfNet *net, Mode m) {
         case Mode::Dropout: return drop_active(net);
         case Mode::BnTrain: return bnt_active(net);
         case Mode::SpecAugment: return sa_active(net);
+        case Mode::LossScale: return net->ls_on;
         case Mode::BackwardN:
         case Mode::XentBackward: break;
     }
@@ -42,6 +43,7 @@ const char *phrase(Mode m) {
         case Mode::Dropout: return "with dropout on (nnet_set_dropout)";
         case Mode::BnTrain: return "with training-mode BatchNorm on (nnet_set_bn_train)";
         case Mode::SpecAugment: return "with SpecAugment on (nnet_set_spec_augment)";
+        case Mode::LossScale: return "with the loss scale on (nnet_set_loss_scale)";
         case Mode::BackwardN:
         case Mode::XentBackward: break;
     }
@@ -69,6 +71,10 @@ const Conflict kConflicts[] = {
     {Mode::RowSubsampling, Mode::BnTrain, nullptr, nullptr, bn_rows_subsampled},
     {Mode::NaturalGradient, Mode::DataParallel, nullptr, nullptr},
     {Mode::DataParallel, Mode::BnTrain, "the statistics would be each rank's own", nullptr},
+    // (the Fisher state is not scale-equivariant across a change of the scale; the MXFP8
+    // backward has block scales of its own)
+    {Mode::LossScale, Mode::NaturalGradient, nullptr, nullptr},
+    {Mode::LossScale, Mode::Fp8, nullptr, nullptr},
     {Mode::BackwardN, Mode::NaturalGradient, nullptr, nullptr},
     {Mode::BackwardN, Mode::Dropout, nullptr, nullptr},
     {Mode::BackwardN, Mode::BnTrain, nullptr, nullptr},

@@ -47,6 +47,14 @@ KF_HIDDEN void set_err(const std::string &s);
 #pragma weak kf_bn_train_bwd_apply_rows
 #pragma weak kf_bn_block_stats
 #pragma weak kf_bn_block_bwd_stats
+#pragma weak kf_loss_scale_state_bytes
+#pragma weak kf_loss_scale_scratch_bytes
+#pragma weak kf_loss_scale_init
+#pragma weak kf_loss_scale_set_scale
+#pragma weak kf_loss_scale_check
+#pragma weak kf_loss_scale_read
+#pragma weak kf_update_maxchange_scaled
+#pragma weak kf_sgd_flat_scaled
 // (a query: against a backend without it nnet_set_row_subsampling decides as it did before it asked)
 #pragma weak kf_gemm_wgrad_halo_applies
 
@@ -271,6 +279,11 @@ struct KfNet {
     void *upd_segs = nullptr, *upd_comps = nullptr, *upd_scratch = nullptr;
     float *upd_stats = nullptr;
     bool upd_ran = false;  // upd_stats holds an update's report
+    // dynamic loss scale (kf_nnet.h nnet_set_loss_scale): the switch, the device state
+    // (kf_ops.h kf_loss_scale_*; made at the first set call, kept when the mode goes off) and the
+    // check pass's per-workgroup flags
+    bool ls_on = false;
+    void *ls_state = nullptr, *ls_flags = nullptr;
     // nnet_constrain_orthonormal: the constrained components (indices into comps, in comps'
     // order), their matrix table on the host and on the device (kf_ops.h KfOrthoMat), scratch
     // and stats, made at the first call and again after nnet_set_component_orthonormal
@@ -471,6 +484,7 @@ inline int list_get(const std::vector<int> &v, int *idx, int n) {
 
 // ---- the modes that cannot all be combined (modes.cpp: the table) ----
 enum class Mode { Fp8, ImplicitDz, RowSubsampling, NaturalGradient, DataParallel, Dropout, BnTrain, SpecAugment,
+                  LossScale,
                   BackwardN /* nnet_backward_n: never "on", only refused */,
                   XentBackward /* nnet_backward_xent: never "on", only refused */ };
 // may `turning_on` be switched on (or nnet_backward_n / nnet_backward_xent run) beside the modes that are on? false

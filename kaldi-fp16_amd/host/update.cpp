@@ -5,10 +5,28 @@
 
 #include "net_internal.h"
 
+static bool upload_update_tables(KfNet *net);
+
+// The loss scale's part of a parameter step, ahead of the update's first launch: the
+// check over the update's segment table and the advance of the state. After it the state says
+// whether this step is skipped and holds 1 / the scale the gradient was made with.
+static bool loss_scale_check(KfNet *net, const char *what) {
+    if (net->upd_dirty && !upload_update_tables(net)) return false;
+    return ck(kf_loss_scale_check(net->ls_state, net->grad, net->nparams, (const KfUpdSegment *)net->upd_segs,
+                                  net->upd_nseg, (int)net->comps.size(), net->ls_flags),
+              what);
+}
+
 extern "C" int nnet_sgd(KfNet *net, float lr, float momentum) {
     kf_take_pending(__func__);
     if (!on_device(net, "sgd")) return -1;
-    if (!ck(kf_sgd_flat(net->master, net->w16, net->grad, net->vel, lr, momentum, net->nparams), "sgd"))
+    if (net->ls_on && !net->comps.empty()) {
+        // (the flat kernel also steps the padding between tensors, as the plain call does)
+        if (!loss_scale_check(net, "sgd: loss scale check") ||
+            !ck(kf_sgd_flat_scaled(net->master, net->w16, net->grad, net->vel, lr, momentum, net->nparams, net->ls_state),
+                "sgd"))
+            return -1;
+    } else if (!ck(kf_sgd_flat(net->master, net->w16, net->grad, net->vel, lr, momentum, net->nparams), "sgd"))
         return -1;
     net->wt_dirty = true;
     // the MXFP8 weight copies follow every parameter change
@@ -114,11 +132,19 @@ extern "C" int nnet_update(KfNet *net, float lr, float momentum, float max_param
     }
     if (net->comps.empty()) return 0;
     if (net->upd_dirty && !upload_update_tables(net)) return -1;
-    if (!ck(kf_update_maxchange(net->master, net->w16, net->grad, net->vel, net->nparams,
-                                (const KfUpdSegment *)net->upd_segs, net->upd_nseg, (const KfUpdComp *)net->upd_comps,
-                                (int)net->comps.size(), lr, momentum, max_param_change, l2_scale, net->upd_scratch,
-                                net->upd_stats),
-            "update"))
+    if (net->ls_on) {
+        if (!loss_scale_check(net, "update: loss scale check") ||
+            !ck(kf_update_maxchange_scaled(net->master, net->w16, net->grad, net->vel, net->nparams,
+                                           (const KfUpdSegment *)net->upd_segs, net->upd_nseg,
+                                           (const KfUpdComp *)net->upd_comps, (int)net->comps.size(), lr, momentum,
+                                           max_param_change, l2_scale, net->upd_scratch, net->upd_stats, net->ls_state),
+                "update"))
+            return -1;
+    } else if (!ck(kf_update_maxchange(net->master, net->w16, net->grad, net->vel, net->nparams,
+                                       (const KfUpdSegment *)net->upd_segs, net->upd_nseg,
+                                       (const KfUpdComp *)net->upd_comps, (int)net->comps.size(), lr, momentum,
+                                       max_param_change, l2_scale, net->upd_scratch, net->upd_stats),
+                   "update"))
         return -1;
     net->upd_ran = true;
     net->wt_dirty = true;
@@ -149,6 +175,65 @@ extern "C" int nnet_update_stats(KfNet *net, float *norms, float *scales, int n,
     if (global_norm) *global_norm = st[2 * ncomp];
     if (global_scale) *global_scale = st[2 * ncomp + 1];
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Dynamic loss scale (kf_nnet.h nnet_set_loss_scale): the switch and the state; the
+// per-step part is loss_scale_check above
+// ---------------------------------------------------------------------------
+extern "C" int nnet_set_loss_scale(KfNet *net, const KfLossScaleOpts *opts) {
+    kf_take_pending(__func__);
+    if (!on_device(net, "set_loss_scale")) return -1;
+    if (!opts) {
+        net->ls_on = false;
+        return 0;
+    }
+    if (!kf_loss_scale_init || !kf_loss_scale_check || !kf_loss_scale_state_bytes || !kf_loss_scale_scratch_bytes ||
+        !kf_loss_scale_set_scale || !kf_loss_scale_read || !kf_update_maxchange_scaled || !kf_sgd_flat_scaled ||
+        !kf_update_scratch_bytes) {
+        set_err("set_loss_scale: this build of libkaldi_fp16 has no loss-scale kernels");
+        return -1;
+    }
+    if (!admit(net, Mode::LossScale, "set_loss_scale")) return -1;
+    // everything a step needs is made here: the update's tables, the state and the flags
+    if (!net->comps.empty() && net->upd_dirty && !upload_update_tables(net)) return -1;
+    if (!net->ls_state) {
+        const long long fb = kf_loss_scale_scratch_bytes(net->nparams, net->upd_nseg);
+        net->ls_state = net->dalloc((size_t)kf_loss_scale_state_bytes());
+        net->ls_flags = fb >= 0 ? net->dalloc((size_t)fb) : nullptr;
+        if (!net->ls_state || !net->ls_flags) {
+            net->ls_state = nullptr;  // (the buffers stay with the net's allocations until it is freed)
+            set_err("set_loss_scale: alloc the state");
+            return -1;
+        }
+    }
+    if (!ck(kf_loss_scale_init(net->ls_state, opts), "set_loss_scale")) return -1;
+    net->ls_on = true;
+    return 0;
+}
+
+extern "C" const float *nnet_loss_scale_ptr(const KfNet *net) {
+    return net && net->ls_on ? (const float *)net->ls_state : nullptr;
+}
+
+extern "C" int nnet_set_loss_scale_value(KfNet *net, float scale) {
+    kf_take_pending(__func__);
+    if (!on_device(net, "set_loss_scale_value")) return -1;
+    if (!net->ls_on) {
+        set_err("set_loss_scale_value: the loss scale is off (nnet_set_loss_scale)");
+        return -1;
+    }
+    return ck(kf_loss_scale_set_scale(net->ls_state, scale), "set_loss_scale_value") ? 0 : -1;
+}
+
+extern "C" int nnet_loss_scale_stats(KfNet *net, float *scale, int *since, long long *steps, long long *skipped,
+                                     int *last_overflow) {
+    if (!on_device(net, "loss_scale_stats")) return -1;
+    if (!net->ls_on) {
+        set_err("loss_scale_stats: the loss scale is off (nnet_set_loss_scale)");
+        return -1;
+    }
+    return ck(kf_loss_scale_read(net->ls_state, scale, since, steps, skipped, last_overflow), "loss_scale_stats") ? 0 : -1;
 }
 
 // ---------------------------------------------------------------------------

@@ -148,6 +148,11 @@ _sig(nnet, "nnet_component_info", _i, _vp, _i, C.c_char_p, _i, _fp, _fp, _fp, C.
 _sig(nnet, "nnet_set_component_opts", _i, _vp, C.c_char_p, _f, _f, _f)
 _sig(nnet, "nnet_update", _i, _vp, _f, _f, _f, _f)
 _sig(nnet, "nnet_update_stats", _i, _vp, _vp, _vp, _i, _fp, _fp)
+# dynamic loss scale (kf_nnet.h nnet_set_loss_scale)
+_sig(nnet, "nnet_set_loss_scale", _i, _vp, _vp)
+_sig(nnet, "nnet_loss_scale_ptr", _vp, _vp)
+_sig(nnet, "nnet_set_loss_scale_value", _i, _vp, _f)
+_sig(nnet, "nnet_loss_scale_stats", _i, _vp, _fp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_ll), C.POINTER(_i))
 _sig(nnet, "nnet_component_orthonormal", _i, _vp, _i, _fp)
 _sig(nnet, "nnet_set_component_orthonormal", _i, _vp, C.c_char_p, _f)
 _sig(nnet, "nnet_orthonormal_components", _i, _vp, C.POINTER(_i), _i)
@@ -552,6 +557,41 @@ class Network:
         check(nnet.nnet_update_stats(self.h, norms.ctypes.data, scales.ctypes.data, n, C.byref(gn), C.byref(gs)),
               "nnet_update_stats")
         return dict(norms=norms, scales=scales, global_norm=gn.value, global_scale=gs.value)
+
+    # Dynamic loss scale (kf_nnet.h nnet_set_loss_scale) ----------------------
+    def set_loss_scale(self, on: bool = True, **opts):
+        """Dynamic loss scaling of the fp16 step, kept on the device: sgd() / update()
+        then check the gradient buffer for a non-finite value, skip the step and halve the scale
+        on one, and unscale by 1 / scale otherwise. The objective has to multiply its derivative
+        by the scale: hand loss_scale_ptr() to Chain.set_grad_scale. opts override
+        kf_loss_scale_default_opts (init_scale 65536, growth 2, backoff 0.5, growth_interval
+        2000, min_scale 1, max_scale 65536). on=False: the plain calls, as before."""
+        if not on:
+            check(nnet.nnet_set_loss_scale(self.h, None), "nnet_set_loss_scale")
+            return
+        o = KfLossScaleOpts()
+        core.kf_loss_scale_default_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in dict(KfLossScaleOpts._fields_):
+                raise TypeError(f"set_loss_scale: unknown option {k}")
+            setattr(o, k, v)
+        check(nnet.nnet_set_loss_scale(self.h, C.byref(o)), "nnet_set_loss_scale")
+
+    def loss_scale_ptr(self):
+        """The device float holding the scale (for Chain.set_grad_scale), None while off."""
+        return nnet.nnet_loss_scale_ptr(self.h)
+
+    def set_loss_scale_value(self, scale: float):
+        """Set the scale (clamped to [min_scale, max_scale]): a checkpoint restore, tests."""
+        check(nnet.nnet_set_loss_scale_value(self.h, float(scale)), "nnet_set_loss_scale_value")
+
+    def loss_scale_stats(self) -> dict:
+        """scale, since, steps, skipped, last_overflow of the loss scale (synchronises)."""
+        s, since, steps, skipped, last = _f(), _i(), _ll(), _ll(), _i()
+        check(nnet.nnet_loss_scale_stats(self.h, C.byref(s), C.byref(since), C.byref(steps), C.byref(skipped),
+                                         C.byref(last)), "nnet_loss_scale_stats")
+        return dict(scale=s.value, since=since.value, steps=steps.value, skipped=skipped.value,
+                    last_overflow=bool(last.value))
 
     # Semi-orthogonal constraint (kf_nnet.h nnet_constrain_orthonormal) -------
     def component_orthonormal(self, name: str) -> float:
@@ -996,6 +1036,23 @@ class KfUpdComp(C.Structure):
 UPD_CHUNK = 4096  # kf_ops.h KF_UPD_CHUNK
 _sig(core, "kf_update_scratch_bytes", _ll, _ll, _i, _i)
 _sig(core, "kf_update_maxchange", _i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp, _vp)
+
+
+# dynamic loss scale (kf_ops.h kf_loss_scale_*, csrc/loss_scale.hip)
+class KfLossScaleOpts(C.Structure):
+    _fields_ = [("init_scale", _f), ("growth", _f), ("backoff", _f), ("growth_interval", _i),
+                ("min_scale", _f), ("max_scale", _f)]
+
+
+_sig(core, "kf_loss_scale_default_opts", None, _vp)
+_sig(core, "kf_loss_scale_state_bytes", _ll)
+_sig(core, "kf_loss_scale_scratch_bytes", _ll, _ll, _i)
+_sig(core, "kf_loss_scale_init", _i, _vp, _vp)
+_sig(core, "kf_loss_scale_set_scale", _i, _vp, _f)
+_sig(core, "kf_loss_scale_check", _i, _vp, _vp, _ll, _vp, _i, _i, _vp)
+_sig(core, "kf_loss_scale_read", _i, _vp, _fp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_ll), C.POINTER(_i))
+_sig(core, "kf_update_maxchange_scaled", _i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp)
+_sig(core, "kf_sgd_flat_scaled", _i, _vp, _vp, _vp, _vp, _f, _f, _ll, _vp)
 
 
 class KfOrthoMat(C.Structure):

@@ -73,6 +73,7 @@ _sig("kf_chain_seq_stats", _vp, _vp)
 _sig("kf_chain_result", _i, _vp, C.POINTER(KfChainResult))
 _sig("kf_chain_xent", _i, _vp, _vp, C.POINTER(KfChainOpts), _vp, _ll, _vp, _ll)
 _sig("kf_chain_xent_result", _i, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig("kf_chain_set_grad_scale", None, _vp, _vp)
 _sig("kf_chain_debug_spin_limit", None, _vp, C.c_uint)
 _sig("kf_chain_debug_exchange_sys", None, _vp, C.c_int)
 _sig("kf_chain_debug_den_pairs", None, _vp, C.c_int)
@@ -249,6 +250,11 @@ class Chain:
         if core.kf_chain_xent_result(self.h, C.byref(o), C.byref(w)) != 0:
             _raise("kf_chain_xent_result")
         return o.value, w.value
+
+    def set_grad_scale(self, ptr):
+        """kf_chain_set_grad_scale: compute() and xent() multiply the finished derivative by the
+        device float at `ptr` (Network.loss_scale_ptr()) before its rounding to fp16; None: off."""
+        core.kf_chain_set_grad_scale(self.h, ptr)
 
     def debug_spin_limit(self, polls: int | None):
         """Test knob: polls before a den exchange wait gives up (None: default)."""

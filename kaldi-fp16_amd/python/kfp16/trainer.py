@@ -125,6 +125,24 @@ class TrainConfig:
     # Both False: the trainer makes exactly the calls it made before.
     apply_deriv_weights: bool = False
     example_weights: bool = False
+    # loss_scale: dynamic loss scaling of the fp16 step, kept on the device. > 0 is the
+    # initial scale (Network.set_loss_scale; the reference's script trains with 65536): the
+    # objective multiplies its derivative by the scale, and step 4 checks the gradient buffer,
+    # skips the step and halves the scale on a non-finite value, and unscales otherwise; after
+    # loss_scale_growth_interval clean steps the scale doubles (at most 65536). A skipped step
+    # still counts in `steps`. Not with natural_gradient. 0: the trainer makes exactly the calls it
+    # made before.
+    loss_scale: float = 0.0
+    loss_scale_growth_interval: int = 2000
+
+    def __post_init__(self):
+        if not (self.loss_scale >= 0.0) or not np.isfinite(self.loss_scale):
+            raise ValueError(f"loss_scale {self.loss_scale}: needs a finite value >= 0 (0: off)")
+        if self.loss_scale_growth_interval < 1:
+            raise ValueError(f"loss_scale_growth_interval {self.loss_scale_growth_interval}: needs >= 1")
+        if self.loss_scale > 0 and self.natural_gradient:
+            raise ValueError("loss_scale is not supported with natural_gradient: the preconditioner's Fisher "
+                             "state is not scale-equivariant across a change of the scale")
 
 
 def parse_dropout_schedule(schedule: str):
@@ -235,6 +253,15 @@ class EgsTrainer:
                 self.net.set_batchnorm_train_sites(self.cfg.batchnorm_train_sites)
             self.net.set_batchnorm_train(True)
             self.net.batchnorm_zero_stats()
+        if self.cfg.loss_scale > 0:
+            self.net.set_loss_scale(True, init_scale=float(self.cfg.loss_scale),
+                                    growth_interval=int(self.cfg.loss_scale_growth_interval),
+                                    max_scale=max(65536.0, float(self.cfg.loss_scale)))
+            self.objective.set_grad_scale(self.net.loss_scale_ptr())
+
+    def loss_scale_stats(self) -> dict:
+        """Network.loss_scale_stats of a trainer with TrainConfig.loss_scale > 0 (synchronises)."""
+        return self.net.loss_scale_stats()
 
     def step(self, batch, allreduce=None, fraction: float | None = None):
         """One TrainStep on `batch` (kfp16.egs.TrainingBatch). allreduce: optional callable
