@@ -379,6 +379,43 @@ int nnet_bn_stats(KfNet *net, const char *layer, int which, double *count, doubl
 int nnet_bn_zero_stats(KfNet *net);
 int nnet_bn_commit(KfNet *net);
 
+/* ReLU unit statistics and self-repair: Kaldi's StoreStats and
+ * RectifiedLinearComponent::RepairGradients on the train step. A site is a ReLU that training-mode
+ * BatchNorm governs: a tdnnf-layer, the big affine of a prefinal-layer or a conv-relu-batchnorm
+ * layer in the current nnet_set_bn_train_sites set with nnet_set_bn_train on; its D columns are
+ * nnet_bn_dim(layer, 0). While the switch is on, every forward in the mode adds, per site, over the
+ * rows its BatchNorm statistics run over: count += n, deriv_sum[c] += #{rows : r > 0} (device
+ * doubles, exact), from the statistics pass that reads r anyway. Every backward first builds each
+ * site's repair vector in one launch: s[c] = -scale S where deriv_sum[c] <= lower count (a dead
+ * unit), +scale S where deriv_sum[c] > upper count (a saturated one), else 0 (and 0 while count
+ * is 0); S is the loss scale's device value, 1 with the loss scale off. The site's
+ * dz = rne_fp16(scale (dy - a - yhat b) relu_bit + s) on the statistics rows: after one nnet_sgd
+ * step with a positive learning rate a dead unit's bias is larger than before. Every step, at the
+ * plain scale (Kaldi: a random half of the minibatches, at twice the scale).
+ *   nnet_set_self_repair: the switch. Where no site exists (training-mode BatchNorm off, or no such
+ *     layer in its sites) it is accepted and no pass changes. Refused beside MXFP8, implicit dz,
+ *     data parallel and nnet_backward_n, in either order. For those refusals the switch counts from
+ *     the moment it is set on a net whose nnet_set_bn_train_sites hold a layer with a ReLU, whether
+ *     training-mode BatchNorm is on or not: while it is set, nnet_set_fp8, nnet_set_implicit_dz,
+ *     nnet_bind_dp and nnet_backward_n fail even though no site is active yet.
+ *   nnet_self_repair_sites: the layer indices of the sites while the mode is on (as nnet_bn_train_layers).
+ *   nnet_self_repair_opts / nnet_set_self_repair_opts: a layer's scale, lower and upper threshold
+ *     (xconfig self-repair-scale, self-repair-lower-threshold, self-repair-upper-threshold; 1e-5,
+ *     0.05, 0.95); scale >= 0 and 0 <= lower < upper <= 1, else -1. Need no device.
+ *   nnet_relu_stats: synchronises. count, and [D] each: value_sum (the BatchNorm accumulator's sum)
+ *     and deriv_sum; value_sum / count and deriv_sum / count are Kaldi's <ValueAvg> and <DerivAvg>
+ *     as long as both kinds were cleared together. Any pointer may be NULL.
+ *   nnet_relu_zero_stats: clears the ReLU statistics and the BatchNorm accumulators
+ *     (nnet_bn_zero_stats): Kaldi's ZeroComponentStats clears both kinds.
+ *   nnet_self_repair_vector: the last backward's s [D] of a site (fp32), for tests and diagnostics. */
+int nnet_set_self_repair(KfNet *net, int on);
+int nnet_self_repair_sites(const KfNet *net, int *idx, int n);
+int nnet_self_repair_opts(const KfNet *net, const char *layer, float *scale, double *lower, double *upper);
+int nnet_set_self_repair_opts(KfNet *net, const char *layer, float scale, double lower, double upper);
+int nnet_relu_stats(KfNet *net, const char *layer, double *count, double *value_sum, double *deriv_sum);
+int nnet_relu_zero_stats(KfNet *net);
+int nnet_self_repair_vector(KfNet *net, const char *layer, float *host);
+
 /* MXFP8 train step (BASELINE configs[4]): 1 = every TDNN-F / linear / prefinal / output
  * GEMM whose input has an MXFP8 copy runs on the fp8 MFMA (kf_ops.h MXFP8 operands);
  * the producing epilogues write those copies, weights are re-quantised on every

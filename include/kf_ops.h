@@ -595,6 +595,54 @@ int kf_bn_block_stats(const void *r, long long ld, int rows, int H, int F, float
 int kf_bn_block_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int H, int F,
                           const float *scale, const float *shift, float target_rms, float *a, float *b);
 
+/* ---- ReLU unit statistics and self-repair (csrc/batchnorm.hip) ----
+ * Kaldi's StoreStats and RectifiedLinearComponent::RepairGradients for a ReLU whose output r the
+ * training-mode BatchNorm entries above read. Same alignment and shape rules as those entries.
+ *
+ * kf_bn_train_stats_relu / kf_bn_block_stats_relu: kf_bn_train_stats / kf_bn_block_stats, and from
+ *   the same pass over r: relu_count[0] += n, relu_deriv[c] += #{rows : r > 0} (device doubles
+ *   [1], [D] or [F]; the counts are integers, exact; fixed order, no atomics). Both NULL: the
+ *   launches and every output bit of the plain entry; one of them NULL: -1.
+ * kf_relu_repair_vectors: one launch for the n sites of a table (given on the host, for the
+ *   checks, and on the device). Per site and column, in double:
+ *     count == 0                 : s = 0
+ *     deriv <= lower count       : s = -scale S   (a dead unit)
+ *     deriv >  upper count       : s = +scale S   (a saturated unit)
+ *     otherwise                  : s = 0
+ *   S = *loss_scale_dev (a device float), 1 when NULL; scale S is one fp32 product. s is fp32 [D],
+ *   16-byte aligned; D % 8 == 0, scale >= 0, 0 <= lower < upper <= 1.
+ * kf_bn_train_bwd_apply_repair / kf_bn_train_bwd_apply_rows_repair: the two apply entries with
+ *   dz = rne_fp16(scale (dy - a - yhat b) relu_bit + repair[c]), the term inside the one rounding
+ *   (so an element whose relu_bit is 0 stores rne_fp16(repair[c])); in the _rows form on the rows
+ *   < stat_rows only, the rows from there on are the plain entry's. repair is fp32 [D], 16-byte
+ *   aligned; NULL is the plain entry. Two launches: the plain entry's kernel, then one that
+ *   evaluates the columns with repair[c] != 0 again on the statistics rows; every other element
+ *   keeps the plain kernel's bits, so an all-zero repair is the plain entry bit for bit. The second
+ *   launch reads g and r again: dz equal to g or r returns -1. */
+typedef struct {
+    const double *count; /* [1] */
+    const double *deriv; /* [D] */
+    float *s;            /* [D] out */
+    int D;
+    float scale;
+    double lower, upper;
+} KfRepairSite;
+int kf_bn_train_stats_relu(const void *r, long long ld, int rows, int D, float eps, float target_rms, float *mean,
+                           float *var, float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq,
+                           double *relu_count, double *relu_deriv);
+int kf_bn_block_stats_relu(const void *r, long long ld, int rows, int H, int F, float eps, float target_rms, float *mean,
+                           float *var, float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq,
+                           double *relu_count, double *relu_deriv);
+int kf_relu_repair_vectors(const KfRepairSite *sites, const KfRepairSite *sites_dev, int n, const float *loss_scale_dev);
+int kf_bn_train_bwd_apply_repair(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                                 const float *scale, const float *shift, float target_rms, const float *a, const float *b,
+                                 const float *drop, long long ld_drop, const int32_t *row_seg, const uint8_t *mask,
+                                 long long ld_mask, void *dz, long long lddz, const float *repair);
+int kf_bn_train_bwd_apply_rows_repair(const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows,
+                                      int D, const float *scale, const float *shift, float target_rms, const float *a,
+                                      const float *b, const float *drop, long long ld_drop, const int32_t *row_seg,
+                                      const uint8_t *mask, long long ld_mask, void *dz, long long lddz, const float *repair);
+
 /* row sets of the row-subsampled train step (kf_nnet.h nnet_set_row_subsampling): compact
  * row c is source row 3c for c < tc0, else (T-1) - 3(tc-1-c). row_bytes % 16 == 0.
  * Every source row must exist: 3(tc0-1) <= T-1 and, with a tail (tc > tc0), its lowest row

@@ -61,12 +61,32 @@ __device__ __forceinline__ void reduce_store(double (&s0)[8], double (&s1)[8], d
     }
 }
 
+// the row lanes' counts of a column (kf_bn_train_stats_relu), added in lane order;
+// cnt[chunk * D + col]. Integers: exact in any order, and the order is fixed all the same.
+__device__ __forceinline__ void reduce_store_count(const int (&n)[8], unsigned *cnt, int D) {
+    __shared__ int redn[kRowLanes][kSlab];
+    const int cx = threadIdx.x % kColLanes, ry = threadIdx.x / kColLanes;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) redn[ry][cx * 8 + e] = n[e];
+    __syncthreads();
+    for (int cl = threadIdx.x; cl < kSlab && blockIdx.x * kSlab + cl < D; cl += kThreads) {
+        int t = redn[0][cl];
+#pragma unroll
+        for (int y = 1; y < kRowLanes; ++y) t += redn[y][cl];
+        cnt[(long long)blockIdx.y * D + blockIdx.x * kSlab + cl] = (unsigned)t;
+    }
+}
+
 // partials of sum r and sum r^2 (one conversion to double per element; its square is exact there)
-__global__ __launch_bounds__(kThreads) void k_bn_fwd_part(const h16 *r, long long ld, int rows, int D, double *part) {
+// COUNT (k_bn_fwd_part_relu only): also the number of elements r > 0, from the same registers.
+// COUNT false is the code the kernel always was, under the symbol it always had.
+template <bool COUNT>
+__device__ __forceinline__ void bn_fwd_part_body(const h16 *r, long long ld, int rows, int D, double *part, unsigned *cnt) {
     const int cx = threadIdx.x % kColLanes, ry = threadIdx.x / kColLanes;
     const int c0 = blockIdx.x * kSlab + cx * 8;
     const int r0 = blockIdx.y * kChunk, r1 = min(rows, r0 + kChunk);
     double s0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (c0 < D) {
 #pragma unroll 4
         for (int m = r0 + ry; m < r1; m += kRowLanes) {
@@ -76,10 +96,19 @@ __global__ __launch_bounds__(kThreads) void k_bn_fwd_part(const h16 *r, long lon
                 const double x = (double)h2f(v[e]);
                 s0[e] += x;
                 s1[e] = fma(x, x, s1[e]);
+                if constexpr (COUNT) n[e] += x > 0.0 ? 1 : 0;
             }
         }
     }
     reduce_store(s0, s1, part, D);
+    if constexpr (COUNT) reduce_store_count(n, cnt, D);
+}
+__global__ __launch_bounds__(kThreads) void k_bn_fwd_part(const h16 *r, long long ld, int rows, int D, double *part) {
+    bn_fwd_part_body<false>(r, ld, rows, D, part, nullptr);
+}
+__global__ __launch_bounds__(kThreads) void k_bn_fwd_part_relu(const h16 *r, long long ld, int rows, int D, double *part,
+                                                                unsigned *cnt) {
+    bn_fwd_part_body<true>(r, ld, rows, D, part, cnt);
 }
 
 // partials of sum dy and sum dy r, dy = g * drop[row_seg[row]] (exact in double)
@@ -140,14 +169,32 @@ __device__ __forceinline__ void sum_chunks(const double *part, int nchunk, int D
 
 // forward: the chunks in order, then mean, var (floored at 0), scale = rms (var + eps)^-1/2 and
 // shift = -mean scale in double, stored in fp32; the accumulators take the sums as they are
-template <int COLS>
-__global__ __launch_bounds__(kThreads) void k_bn_fwd_finish(const double *part, int nchunk, double rows, int D, double eps,
-                                                            double rms, float *mean, float *var, float *scale,
-                                                            float *shift, double *acc_count, double *acc_sum,
-                                                            double *acc_sumsq) {
+// COUNT (k_bn_fwd_finish_relu only): the chunks' counts of r > 0 in the same order, into
+// the ReLU statistics relu_count += rows, relu_deriv[c] += count (doubles holding integers: exact)
+template <int COLS, bool COUNT>
+__device__ __forceinline__ void bn_fwd_finish_body(const double *part, int nchunk, double rows, int D, double eps, double rms,
+                                                   float *mean, float *var, float *scale, float *shift, double *acc_count,
+                                                   double *acc_sum, double *acc_sumsq, const unsigned *cnt,
+                                                   double *relu_count, double *relu_deriv) {
     const int c = blockIdx.x * COLS + threadIdx.x % COLS, lane = threadIdx.x / COLS;
     double s, q;
     sum_chunks<COLS>(part, nchunk, D, c, lane, s, q);
+    if constexpr (COUNT) {
+        constexpr int LANES = kThreads / COLS;
+        __shared__ unsigned long long redn[LANES][COLS];
+        unsigned long long n0 = 0;
+        if (c < D)
+            for (int k = lane; k < nchunk; k += LANES) n0 += cnt[(long long)k * D + c];
+        redn[lane][threadIdx.x % COLS] = n0;
+        __syncthreads();
+        if (c < D && lane == 0) {
+            unsigned long long n = redn[0][threadIdx.x % COLS];
+#pragma unroll
+            for (int l = 1; l < LANES; ++l) n += redn[l][threadIdx.x % COLS];
+            relu_deriv[c] += (double)n;
+            if (c == 0) relu_count[0] += rows;
+        }
+    }
     if (c >= D || lane != 0) return;
     const double mu = s / rows;
     double v = q / rows - mu * mu;
@@ -162,6 +209,23 @@ __global__ __launch_bounds__(kThreads) void k_bn_fwd_finish(const double *part, 
         acc_sumsq[c] += q;
         if (c == 0) acc_count[0] += rows;
     }
+}
+template <int COLS>
+__global__ __launch_bounds__(kThreads) void k_bn_fwd_finish(const double *part, int nchunk, double rows, int D, double eps,
+                                                            double rms, float *mean, float *var, float *scale,
+                                                            float *shift, double *acc_count, double *acc_sum,
+                                                            double *acc_sumsq) {
+    bn_fwd_finish_body<COLS, false>(part, nchunk, rows, D, eps, rms, mean, var, scale, shift, acc_count, acc_sum, acc_sumsq,
+                                    nullptr, nullptr, nullptr);
+}
+template <int COLS>
+__global__ __launch_bounds__(kThreads) void k_bn_fwd_finish_relu(const double *part, int nchunk, double rows, int D, double eps,
+                                                                 double rms, float *mean, float *var, float *scale,
+                                                                 float *shift, double *acc_count, double *acc_sum,
+                                                                 double *acc_sumsq, const unsigned *cnt, double *relu_count,
+                                                                 double *relu_deriv) {
+    bn_fwd_finish_body<COLS, true>(part, nchunk, rows, D, eps, rms, mean, var, scale, shift, acc_count, acc_sum, acc_sumsq, cnt,
+                                   relu_count, relu_deriv);
 }
 
 // backward: a = sum dy / n, b = sum dy yhat / n with yhat = (r scale + shift) / rms, so
@@ -235,11 +299,32 @@ __device__ __forceinline__ void blk_reduce_store(double (&s0)[8], double (&s1)[8
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_bnb_fwd_part(const h16 *r, long long ld, int rows, int H, int F, int cw,
-                                                           double *part) {
+// the positions' counts of a column (kf_bn_block_stats_relu), added in position order; cnt[chunk * F + col]
+__device__ __forceinline__ void blk_reduce_store_count(const int (&n)[8], unsigned *cnt, int F, int cw) {
+    __shared__ int redn[8][kThreads];
+    const int P = kThreads / cw;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) redn[e][threadIdx.x] = n[e];
+    __syncthreads();
+    for (int j = threadIdx.x; j < cw * 8; j += kThreads) {
+        const int c = j % cw, e = j / cw;
+        const int col = (blockIdx.x * kThreads + c) * 8 + e;
+        if (col < F) {
+            int t = redn[e][c];
+            for (int p = 1; p < P; ++p) t += redn[e][p * cw + c];
+            cnt[(long long)blockIdx.y * F + col] = (unsigned)t;
+        }
+    }
+}
+
+// COUNT (k_bnb_fwd_part_relu only): also the number of elements r > 0; false is the kernel as it was
+template <bool COUNT>
+__device__ __forceinline__ void bnb_fwd_part_body(const h16 *r, long long ld, int rows, int H, int F, int cw, double *part,
+                                                  unsigned *cnt) {
     const BlkLane l = blk_lane(F, cw);
     const int r0 = blockIdx.y * kBlkRows, r1 = min(rows, r0 + kBlkRows);
     double s0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (l.on) {
         const long long nq = (long long)(r1 - r0) * H;  // block rows of this workgroup
         const int dr = l.P / H, dh = l.P % H;
@@ -253,6 +338,7 @@ __global__ __launch_bounds__(kThreads) void k_bnb_fwd_part(const h16 *r, long lo
                 const double x = (double)h2f(v[e]);
                 s0[e] += x;
                 s1[e] = fma(x, x, s1[e]);
+                if constexpr (COUNT) n[e] += x > 0.0 ? 1 : 0;
             }
             row += dr;
             h += dh;
@@ -260,6 +346,15 @@ __global__ __launch_bounds__(kThreads) void k_bnb_fwd_part(const h16 *r, long lo
         }
     }
     blk_reduce_store(s0, s1, part, F, cw);
+    if constexpr (COUNT) blk_reduce_store_count(n, cnt, F, cw);
+}
+__global__ __launch_bounds__(kThreads) void k_bnb_fwd_part(const h16 *r, long long ld, int rows, int H, int F, int cw,
+                                                           double *part) {
+    bnb_fwd_part_body<false>(r, ld, rows, H, F, cw, part, nullptr);
+}
+__global__ __launch_bounds__(kThreads) void k_bnb_fwd_part_relu(const h16 *r, long long ld, int rows, int H, int F, int cw,
+                                                                double *part, unsigned *cnt) {
+    bnb_fwd_part_body<true>(r, ld, rows, H, F, cw, part, cnt);
 }
 
 __global__ __launch_bounds__(kThreads) void k_bnb_bwd_part(const h16 *g, long long ldg, const h16 *r, long long ldr,
@@ -345,16 +440,36 @@ __global__ __launch_bounds__(kThreads) void k_bn_fwd_apply(const h16 *r, long lo
 // the kernel always was (stat_rows unused), under the symbol it always had (k_bn_bwd_apply), so
 // kf_bn_train_bwd_apply's bits cannot move; k_bn_bwd_apply_rows is the body with the threshold.
 constexpr int kApplyRows = 4;
-template <bool DROP, bool MASK, bool ROWS>
+template <bool DROP, bool MASK, bool ROWS, bool REPAIR = false>
 __device__ __forceinline__ void bn_bwd_apply_body(const h16 *g, long long ldg, const h16 *r, long long ldr, int rows,
                                                   int stat_rows, long long units, int d8, const float *scale,
                                                   const float *shift, double inv_rms, const float *a, const float *b,
                                                   Drop dr, const uint8_t *mask, long long ld_mask, h16 *dz, long long lddz,
-                                                  unsigned ones) {
+                                                  unsigned ones, const float *repair = nullptr) {
     const long long u = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (u >= units) return;
     const long long grp = u / d8;
     const int c0 = (int)(u - grp * d8) * 8;
+    // REPAIR (k_bn_bwd_apply_repair, behind the plain kernel on the stream): the columns whose
+    // self-repair term is not zero are evaluated again with the term inside the one rounding, and
+    // an element whose relu_bit is 0 stores the term alone. Every other column keeps the bits the
+    // plain kernel stored (how that kernel rounds a column rests on the compiler, see MASK above:
+    // nothing here may stand in for it), and a group of 8 columns without a term is not touched: its
+    // lanes load the 32 bytes of the term and return, before any other load.
+    double sr[8];
+    bool nz[8];
+    if constexpr (REPAIR) {
+        float s[8];
+        load_f8(repair + c0, s);
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            sr[e] = (double)s[e];
+            nz[e] = s[e] != 0.f;
+            any = any || nz[e];
+        }
+        if (!any) return;
+    }
     float sc[8], sh[8], av[8], bv[8];
     load_f8(scale + c0, sc);
     load_f8(shift + c0, sh);
@@ -385,7 +500,13 @@ __device__ __forceinline__ void bn_bwd_apply_body(const h16 *g, long long ldg, c
                 double dy = (double)h2f(gv[e]);
                 if constexpr (DROP) dy *= (double)d[e];
                 const double w = fma(scd[e], dy, -fma(k1[e], (double)h2f(rv[e]), k0[e]));
-                o[e] = ((bits >> e) & 1u) ? f2h((float)w) : (h16)0.f;
+                if constexpr (REPAIR) o[e] = f2h((float)((((bits >> e) & 1u) ? w : 0.0) + sr[e]));
+                else o[e] = ((bits >> e) & 1u) ? f2h((float)w) : (h16)0.f;
+            }
+            if constexpr (REPAIR) {
+                const half8 plain = load_h8(dz + m * lddz + c0);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = nz[e] ? o[e] : plain[e];
             }
         } else {
 #pragma unroll
@@ -418,6 +539,39 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply_rows(const h16 *g, lo
                                         ld_mask, dz, lddz, ones);
 }
 
+// kf_bn_train_bwd_apply_repair / _rows_repair: the body above with the repair term,
+// over the statistics rows and the columns with a term only, behind the plain kernel (bwd_apply
+// below); kernels of their own, so the eight above keep their code.
+template <bool DROP, bool MASK>
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply_repair(const h16 *g, long long ldg, const h16 *r, long long ldr,
+                                                                  int rows, long long units, int d8, const float *scale,
+                                                                  const float *shift, double inv_rms, const float *a,
+                                                                  const float *b, Drop dr, const uint8_t *mask,
+                                                                  long long ld_mask, h16 *dz, long long lddz, unsigned ones,
+                                                                  const float *repair) {
+    bn_bwd_apply_body<DROP, MASK, false, true>(g, ldg, r, ldr, rows, rows, units, d8, scale, shift, inv_rms, a, b, dr, mask,
+                                               ld_mask, dz, lddz, ones, repair);
+}
+
+// s = -k S, +k S or 0 per column of every site of a backward (kf_relu_repair_vectors):
+// blockIdx.y = site, a lane = 4 columns, the comparisons in double. D % 4 == 0 (the entry checks
+// D % 8), s 16-byte aligned: one 16-byte vector store per lane.
+__global__ __launch_bounds__(kThreads) void k_relu_repair_vectors(const KfRepairSite *sites, const float *loss_scale) {
+    const KfRepairSite st = sites[blockIdx.y];
+    const int c0 = (blockIdx.x * kThreads + threadIdx.x) * 4;
+    if (c0 >= st.D) return;
+    const double count = st.count[0];
+    const float ks = st.scale * (loss_scale ? loss_scale[0] : 1.f);
+    const double lo = (double)st.lower * count, hi = (double)st.upper * count;
+    float4v o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const double d = st.deriv[c0 + e];
+        o[e] = count == 0.0 ? 0.f : d <= lo ? -ks : d > hi ? ks : 0.f;
+    }
+    *reinterpret_cast<float4v *>(st.s + c0) = o;
+}
+
 bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // shape rules shared by the four entries: rows x D fp16 tensors read with 16-byte lanes
@@ -448,10 +602,52 @@ bool launched(const char *what) {
     return false;
 }
 int chunks_of(int rows) { return (rows + kChunk - 1) / kChunk; }
-double *partials(const char *what, int rows, int D) {
-    double *p = (double *)kf_workspace_stream((size_t)chunks_of(rows) * 2 * D * sizeof(double));
+// planes = 3: room for the _relu entries' counts (unsigned, half of the third plane) behind the sums
+double *partials(const char *what, int rows, int D, int planes = 2) {
+    double *p = (double *)kf_workspace_stream((size_t)chunks_of(rows) * planes * D * sizeof(double));
     if (!p) kf_report_error("%s: workspace", what);
     return p;
+}
+
+}  // namespace
+
+namespace {
+
+// the ReLU statistics of the _relu entries: both or none
+bool relu_acc_ok(const char *what, const double *relu_count, const double *relu_deriv) {
+    if (!relu_count == !relu_deriv) return true;
+    kf_report_error("%s: needs relu_count and relu_deriv, or neither", what);
+    return false;
+}
+
+// kf_bn_train_stats / _relu. relu_deriv == NULL launches the two kernels kf_bn_train_stats always
+// launched; else the counting pair, whose count partials lie behind the sums' in the scratch.
+int fwd_stats(const char *what, const void *r, long long ld, int rows, int D, float eps, float target_rms, float *mean, float *var,
+              float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq, double *relu_count,
+              double *relu_deriv) {
+    if (!shape_ok(what, rows, D) || !tensor_ok(what, "r", r, ld, D) || !relu_acc_ok(what, relu_count, relu_deriv)) return -1;
+    if (!mean || !var || !scale || !shift || !(eps >= 0.f) || !(target_rms > 0.f) ||
+        ((acc_count || acc_sum || acc_sumsq) && !(acc_count && acc_sum && acc_sumsq))) {
+        kf_report_error("%s: needs mean, var, scale, shift, eps >= 0, target_rms > 0 and all three accumulators or none", what);
+        return -1;
+    }
+    const int nchunk = chunks_of(rows);
+    double *part = partials(what, rows, D, relu_deriv ? 3 : 2);
+    if (!part) return -1;
+    const dim3 grid((unsigned)((D + kSlab - 1) / kSlab), (unsigned)nchunk);
+    const unsigned fin = (unsigned)((D + kFinCols - 1) / kFinCols);
+    if (relu_deriv) {
+        unsigned *cnt = (unsigned *)(part + (size_t)nchunk * 2 * D);
+        k_bn_fwd_part_relu<<<grid, kThreads, 0, kf_stream()>>>((const h16 *)r, ld, rows, D, part, cnt);
+        k_bn_fwd_finish_relu<kFinCols><<<fin, kThreads, 0, kf_stream()>>>(part, nchunk, (double)rows, D, (double)eps,
+                                                                          (double)target_rms, mean, var, scale, shift, acc_count,
+                                                                          acc_sum, acc_sumsq, cnt, relu_count, relu_deriv);
+        return launched(what) ? 0 : -1;
+    }
+    k_bn_fwd_part<<<grid, kThreads, 0, kf_stream()>>>((const h16 *)r, ld, rows, D, part);
+    k_bn_fwd_finish<kFinCols><<<fin, kThreads, 0, kf_stream()>>>(part, nchunk, (double)rows, D, (double)eps, (double)target_rms,
+                                                                 mean, var, scale, shift, acc_count, acc_sum, acc_sumsq);
+    return launched(what) ? 0 : -1;
 }
 
 }  // namespace
@@ -460,21 +656,16 @@ extern "C" int kf_bn_train_stats(const void *r, long long ld, int rows, int D, f
                                  float *var, float *scale, float *shift, double *acc_count, double *acc_sum,
                                  double *acc_sumsq) {
     kf_take_pending(__func__);
-    const char *what = "kf_bn_train_stats";
-    if (!shape_ok(what, rows, D) || !tensor_ok(what, "r", r, ld, D)) return -1;
-    if (!mean || !var || !scale || !shift || !(eps >= 0.f) || !(target_rms > 0.f) ||
-        ((acc_count || acc_sum || acc_sumsq) && !(acc_count && acc_sum && acc_sumsq))) {
-        kf_report_error("%s: needs mean, var, scale, shift, eps >= 0, target_rms > 0 and all three accumulators or none", what);
-        return -1;
-    }
-    double *part = partials(what, rows, D);
-    if (!part) return -1;
-    const int nchunk = chunks_of(rows);
-    const dim3 grid((unsigned)((D + kSlab - 1) / kSlab), (unsigned)nchunk);
-    k_bn_fwd_part<<<grid, kThreads, 0, kf_stream()>>>((const h16 *)r, ld, rows, D, part);
-    k_bn_fwd_finish<kFinCols><<<(unsigned)((D + kFinCols - 1) / kFinCols), kThreads, 0, kf_stream()>>>(
-        part, nchunk, (double)rows, D, (double)eps, (double)target_rms, mean, var, scale, shift, acc_count, acc_sum, acc_sumsq);
-    return launched(what) ? 0 : -1;
+    return fwd_stats("kf_bn_train_stats", r, ld, rows, D, eps, target_rms, mean, var, scale, shift, acc_count, acc_sum, acc_sumsq,
+                     nullptr, nullptr);
+}
+
+extern "C" int kf_bn_train_stats_relu(const void *r, long long ld, int rows, int D, float eps, float target_rms, float *mean,
+                                      float *var, float *scale, float *shift, double *acc_count, double *acc_sum,
+                                      double *acc_sumsq, double *relu_count, double *relu_deriv) {
+    kf_take_pending(__func__);
+    return fwd_stats("kf_bn_train_stats_relu", r, ld, rows, D, eps, target_rms, mean, var, scale, shift, acc_count, acc_sum,
+                     acc_sumsq, relu_count, relu_deriv);
 }
 
 extern "C" int kf_bn_train_apply(const void *r, long long ld, int rows, int D, const float *scale, const float *shift,
@@ -527,10 +718,12 @@ int bwd_stats(const char *what, const void *g, long long ldg, const void *r, lon
 // the one kf_bn_train_bwd_apply always launched.
 int bwd_apply(const char *what, const void *g, long long ldg, const void *r, long long ldr, int rows, int stat_rows, int D,
               const float *scale, const float *shift, float target_rms, const float *a, const float *b, const float *drop,
-              long long ld_drop, const int32_t *row_seg, const uint8_t *mask, long long ld_mask, void *dz, long long lddz) {
+              long long ld_drop, const int32_t *row_seg, const uint8_t *mask, long long ld_mask, void *dz, long long lddz,
+              const float *repair = nullptr) {
     if (!shape_ok(what, rows, D) || !tensor_ok(what, "g", g, ldg, D) || !tensor_ok(what, "r", r, ldr, D) ||
         !tensor_ok(what, "dz", dz, lddz, D) || !cols_ok(what, "scale", scale) || !cols_ok(what, "shift", shift) ||
-        !cols_ok(what, "a", a) || !cols_ok(what, "b", b) || !drop_ok(what, drop, ld_drop, row_seg, D))
+        !cols_ok(what, "a", a) || !cols_ok(what, "b", b) || !drop_ok(what, drop, ld_drop, row_seg, D) ||
+        (repair && !cols_ok(what, "repair", repair)))
         return -1;
     if ((mask && (ld_mask < D || ld_mask % 8)) || !(target_rms > 0.f)) {
         kf_report_error("%s: needs the ReLU mask with ld_mask >= D bits, ld_mask %% 8 == 0 (or none), and target_rms > 0", what);
@@ -538,6 +731,10 @@ int bwd_apply(const char *what, const void *g, long long ldg, const void *r, lon
     }
     if (stat_rows < 1 || stat_rows > rows) {
         kf_report_error("%s: needs 1 <= stat_rows <= rows (stat_rows=%d rows=%d)", what, stat_rows, rows);
+        return -1;
+    }
+    if (repair && (dz == g || dz == r)) {  // (the second launch reads g and r again behind the first one's stores)
+        kf_report_error("%s: dz may not alias g or r", what);
         return -1;
     }
     const int d8 = D / 8;
@@ -560,6 +757,20 @@ int bwd_apply(const char *what, const void *g, long long ldg, const void *r, lon
         else KF_BN_BWD_APPLY((k_bn_bwd_apply<false, false>), );
     }
 #undef KF_BN_BWD_APPLY
+    if (repair) {
+        // the plain kernel above wrote every row; the columns with a term again, on the statistics rows
+        const long long sunits = (long long)((stat_rows + kApplyRows - 1) / kApplyRows) * d8;
+        const unsigned sblk = (unsigned)((sunits + kThreads - 1) / kThreads);
+#define KF_BN_BWD_REPAIR(DROP, MASK)                                                                                        \
+    k_bn_bwd_apply_repair<DROP, MASK><<<sblk, kThreads, 0, kf_stream()>>>((const h16 *)g, ldg, (const h16 *)r, ldr, stat_rows,    \
+                                                                          sunits, d8, scale, shift, inv_rms, a, b, dr, mask,     \
+                                                                          ld_mask, (h16 *)dz, lddz, 0xFFu, repair)
+        if (drop && mask) KF_BN_BWD_REPAIR(true, true);
+        else if (mask) KF_BN_BWD_REPAIR(false, true);
+        else if (drop) KF_BN_BWD_REPAIR(true, false);
+        else KF_BN_BWD_REPAIR(false, false);
+#undef KF_BN_BWD_REPAIR
+    }
     return launched(what) ? 0 : -1;
 }
 
@@ -599,6 +810,50 @@ extern "C" int kf_bn_train_bwd_apply_rows(const void *g, long long ldg, const vo
                      ld_drop, row_seg, mask, ld_mask, dz, lddz);
 }
 
+extern "C" int kf_bn_train_bwd_apply_repair(const void *g, long long ldg, const void *r, long long ldr, int rows, int D,
+                                            const float *scale, const float *shift, float target_rms, const float *a,
+                                            const float *b, const float *drop, long long ld_drop, const int32_t *row_seg,
+                                            const uint8_t *mask, long long ld_mask, void *dz, long long lddz,
+                                            const float *repair) {
+    kf_take_pending(__func__);
+    return bwd_apply("kf_bn_train_bwd_apply_repair", g, ldg, r, ldr, rows, rows, D, scale, shift, target_rms, a, b, drop, ld_drop,
+                     row_seg, mask, ld_mask, dz, lddz, repair);
+}
+
+extern "C" int kf_bn_train_bwd_apply_rows_repair(const void *g, long long ldg, const void *r, long long ldr, int rows,
+                                                 int stat_rows, int D, const float *scale, const float *shift, float target_rms,
+                                                 const float *a, const float *b, const float *drop, long long ld_drop,
+                                                 const int32_t *row_seg, const uint8_t *mask, long long ld_mask, void *dz,
+                                                 long long lddz, const float *repair) {
+    kf_take_pending(__func__);
+    return bwd_apply("kf_bn_train_bwd_apply_rows_repair", g, ldg, r, ldr, rows, stat_rows, D, scale, shift, target_rms, a, b, drop,
+                     ld_drop, row_seg, mask, ld_mask, dz, lddz, repair);
+}
+
+extern "C" int kf_relu_repair_vectors(const KfRepairSite *sites, const KfRepairSite *sites_dev, int n,
+                                      const float *loss_scale_dev) {
+    kf_take_pending(__func__);
+    const char *what = "kf_relu_repair_vectors";
+    if (!sites || !sites_dev || n < 1 || n > 65535) {
+        kf_report_error("%s: needs the table on the host and on the device and 1 <= n <= 65535 (n=%d)", what, n);
+        return -1;
+    }
+    int maxd = 0;
+    for (int i = 0; i < n; ++i) {
+        const KfRepairSite &s = sites[i];
+        if (!s.count || !s.deriv || !s.s || !al16(s.s) || s.D <= 0 || s.D % 8 || !(s.scale >= 0.f) ||
+            !(s.lower >= 0.f && s.lower < s.upper && s.upper <= 1.f)) {
+            kf_report_error("%s: site %d needs count, deriv, a 16-byte aligned s, D > 0, D %% 8 == 0, scale >= 0 and "
+                            "0 <= lower < upper <= 1 (D=%d)", what, i, s.D);
+            return -1;
+        }
+        maxd = std::max(maxd, s.D);
+    }
+    const dim3 grid((unsigned)((maxd / 4 + kThreads - 1) / kThreads), (unsigned)n);
+    k_relu_repair_vectors<<<grid, kThreads, 0, kf_stream()>>>(sites_dev, loss_scale_dev);
+    return launched(what) ? 0 : -1;
+}
+
 // ---- block statistics: the entries ----
 namespace {
 
@@ -618,10 +873,47 @@ bool block_tensor_ok(const char *what, const char *name, const void *p, long lon
 int block_chunks(int rows) { return (rows + kBlkRows - 1) / kBlkRows; }
 int block_cw(int F) { return std::min(F / 8, kThreads); }
 dim3 block_grid(int rows, int F) { return dim3((unsigned)((F / 8 + kThreads - 1) / kThreads), (unsigned)block_chunks(rows)); }
-double *block_partials(const char *what, int rows, int F) {
-    double *p = (double *)kf_workspace_stream((size_t)block_chunks(rows) * 2 * F * sizeof(double));
+double *block_partials(const char *what, int rows, int F, int planes = 2) {
+    double *p = (double *)kf_workspace_stream((size_t)block_chunks(rows) * planes * F * sizeof(double));
     if (!p) kf_report_error("%s: workspace", what);
     return p;
+}
+
+}  // namespace
+
+namespace {
+
+// kf_bn_block_stats / _relu, as fwd_stats above
+int block_fwd_stats(const char *what, const void *r, long long ld, int rows, int H, int F, float eps, float target_rms,
+                    float *mean, float *var, float *scale, float *shift, double *acc_count, double *acc_sum, double *acc_sumsq,
+                    double *relu_count, double *relu_deriv) {
+    if (!block_shape_ok(what, rows, H, F) || !block_tensor_ok(what, "r", r, ld, H, F) ||
+        !relu_acc_ok(what, relu_count, relu_deriv))
+        return -1;
+    if (!mean || !var || !scale || !shift || !(eps >= 0.f) || !(target_rms > 0.f) ||
+        ((acc_count || acc_sum || acc_sumsq) && !(acc_count && acc_sum && acc_sumsq))) {
+        kf_report_error("%s: needs mean, var, scale, shift, eps >= 0, target_rms > 0 and all three accumulators or none", what);
+        return -1;
+    }
+    const int nchunk = block_chunks(rows);
+    double *part = block_partials(what, rows, F, relu_deriv ? 3 : 2);
+    if (!part) return -1;
+    const unsigned fin = (unsigned)((F + kBlkFinCols - 1) / kBlkFinCols);
+    if (relu_deriv) {
+        unsigned *cnt = (unsigned *)(part + (size_t)nchunk * 2 * F);
+        k_bnb_fwd_part_relu<<<block_grid(rows, F), kThreads, 0, kf_stream()>>>((const h16 *)r, ld, rows, H, F, block_cw(F), part,
+                                                                               cnt);
+        k_bn_fwd_finish_relu<kBlkFinCols><<<fin, kThreads, 0, kf_stream()>>>(part, nchunk, (double)rows * H, F, (double)eps,
+                                                                             (double)target_rms, mean, var, scale, shift,
+                                                                             acc_count, acc_sum, acc_sumsq, cnt, relu_count,
+                                                                             relu_deriv);
+        return launched(what) ? 0 : -1;
+    }
+    k_bnb_fwd_part<<<block_grid(rows, F), kThreads, 0, kf_stream()>>>((const h16 *)r, ld, rows, H, F, block_cw(F), part);
+    k_bn_fwd_finish<kBlkFinCols><<<fin, kThreads, 0, kf_stream()>>>(part, nchunk, (double)rows * H, F, (double)eps,
+                                                                    (double)target_rms, mean, var, scale, shift, acc_count,
+                                                                    acc_sum, acc_sumsq);
+    return launched(what) ? 0 : -1;
 }
 
 }  // namespace
@@ -630,20 +922,16 @@ extern "C" int kf_bn_block_stats(const void *r, long long ld, int rows, int H, i
                                  float *mean, float *var, float *scale, float *shift, double *acc_count, double *acc_sum,
                                  double *acc_sumsq) {
     kf_take_pending(__func__);
-    const char *what = "kf_bn_block_stats";
-    if (!block_shape_ok(what, rows, H, F) || !block_tensor_ok(what, "r", r, ld, H, F)) return -1;
-    if (!mean || !var || !scale || !shift || !(eps >= 0.f) || !(target_rms > 0.f) ||
-        ((acc_count || acc_sum || acc_sumsq) && !(acc_count && acc_sum && acc_sumsq))) {
-        kf_report_error("%s: needs mean, var, scale, shift, eps >= 0, target_rms > 0 and all three accumulators or none", what);
-        return -1;
-    }
-    double *part = block_partials(what, rows, F);
-    if (!part) return -1;
-    k_bnb_fwd_part<<<block_grid(rows, F), kThreads, 0, kf_stream()>>>((const h16 *)r, ld, rows, H, F, block_cw(F), part);
-    k_bn_fwd_finish<kBlkFinCols><<<(unsigned)((F + kBlkFinCols - 1) / kBlkFinCols), kThreads, 0, kf_stream()>>>(
-        part, block_chunks(rows), (double)rows * H, F, (double)eps, (double)target_rms, mean, var, scale, shift, acc_count,
-        acc_sum, acc_sumsq);
-    return launched(what) ? 0 : -1;
+    return block_fwd_stats("kf_bn_block_stats", r, ld, rows, H, F, eps, target_rms, mean, var, scale, shift, acc_count, acc_sum,
+                           acc_sumsq, nullptr, nullptr);
+}
+
+extern "C" int kf_bn_block_stats_relu(const void *r, long long ld, int rows, int H, int F, float eps, float target_rms,
+                                      float *mean, float *var, float *scale, float *shift, double *acc_count, double *acc_sum,
+                                      double *acc_sumsq, double *relu_count, double *relu_deriv) {
+    kf_take_pending(__func__);
+    return block_fwd_stats("kf_bn_block_stats_relu", r, ld, rows, H, F, eps, target_rms, mean, var, scale, shift, acc_count,
+                           acc_sum, acc_sumsq, relu_count, relu_deriv);
 }
 
 extern "C" int kf_bn_block_bwd_stats(const void *g, long long ldg, const void *r, long long ldr, int rows, int H, int F,

@@ -313,7 +313,8 @@ struct BackwardPass {
     bool bn_train_dz(Step &s, int ib);
     bool bn_rows_entries();
     bool bn_site_dz(const void *g, const void *r, int rows, int stat_rows, int H, int F, const float *stat, float rms,
-                    const uint8_t *mask, void *dz_out, const std::string &what);
+                    const uint8_t *mask, void *dz_out, const std::string &what, const float *repair = nullptr);
+    bool repair_vectors();
     void *bn_site_slot(const NetLayer &nl);
     bool tdnnf_affine_wgrad(Step &s, const Tdnnf &t), tdnnf_affine_dgrad(Step &s, const Tdnnf &t);
     bool tdnnf_affine_dgrad_mx(Step &s, const Tdnnf &t, const KfEpilogue &E1, void *edge);
@@ -444,7 +445,23 @@ bool BackwardPass::begin() {
             net->rm_tc = net->rs.Tc;
         }
     }
-    return true;
+    return repair_vectors();
+}
+
+// Self-repair: every site's repair vector in one launch on the chain stream, before the
+// first step, from the accumulators as the forward left them (begin() put this stream behind the
+// forward's) and the loss scale's device value. The sites' steps add them inside dz's rounding.
+bool BackwardPass::repair_vectors() {
+    bool any = false;
+    for (int li : net->sr_sites) any = any || net->layers[li].sr_act;
+    if (!any) return true;
+    if (!kf_relu_repair_vectors || !kf_bn_train_bwd_apply_repair || !kf_bn_train_bwd_apply_rows_repair) {
+        set_err("backward: this build of libkaldi_fp16 has no self-repair kernels");
+        return false;
+    }
+    return ck(kf_relu_repair_vectors(net->sr_tab.data(), (const KfRepairSite *)net->sr_tab_dev, (int)net->sr_tab.size(),
+                                     net->ls_on ? (const float *)net->ls_state : nullptr),
+              "self-repair vectors");
 }
 
 // The xent branch before the chain walk: ordinary steps seeded with the xent output's gradient,
@@ -677,7 +694,7 @@ bool BackwardPass::prefinal(Step &s) {
     KfOperand B1 = op_base(wptr(net, nl.pW2), small, big, small, 1);
     if (!ck(kf_gemm_fused(T, big, small, &A1, &B1, &E1), "prefinal small dgrad")) return false;
     if (bnt && !bn_site_dz(gbig, nl.bnt_r, T, bnt_stat_rows(net, s.li), 1, big, nl.bnt_stat, nl.bn_rms, nl.mask, dzbig,
-                           "prefinal " + nl.L.name + " (big)"))
+                           "prefinal " + nl.L.name + " (big)", nl.sr_act ? nl.sr_s : nullptr))
         return false;
     KfOperand A3 = op_base(s.x, din, T, din, 0);
     KfOperand B3 = op_base(dzbig, big, T, big, 0);
@@ -796,18 +813,26 @@ bool BackwardPass::bn_train_dz(Step &s, int ib) {
     // compact rows: the statistics were those of the rows c < Tc0, so the sums run over
     // all Tc rows with the divisor Tc0 and only those rows take the correction
     const int Ts = bnt_stat_rows(net, s.li);
+    // self-repair: the site's term inside the apply's rounding, on the statistics rows
+    const float *repair = nl.sr_act ? nl.sr_s : nullptr;
     if (Ts < T) {
         if (!bn_rows_entries()) return false;
-        return ck(kf_bn_train_bwd_stats_rows(gcur, D, nl.bnt_r, D, T, Ts, D, sc, sh, nl.bn_rms, drop, D, rseg, a, b),
-                  "tdnnf batchnorm backward statistics") &&
-               ck(kf_bn_train_bwd_apply_rows(gcur, D, nl.bnt_r, D, T, Ts, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
-                                             net->dz[ib], D),
+        if (!ck(kf_bn_train_bwd_stats_rows(gcur, D, nl.bnt_r, D, T, Ts, D, sc, sh, nl.bn_rms, drop, D, rseg, a, b),
+                "tdnnf batchnorm backward statistics"))
+            return false;
+        return ck(repair ? kf_bn_train_bwd_apply_rows_repair(gcur, D, nl.bnt_r, D, T, Ts, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg,
+                                                             nl.mask, D, net->dz[ib], D, repair)
+                         : kf_bn_train_bwd_apply_rows(gcur, D, nl.bnt_r, D, T, Ts, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg,
+                                                      nl.mask, D, net->dz[ib], D),
                   "tdnnf batchnorm backward apply");
     }
-    return ck(kf_bn_train_bwd_stats(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, drop, D, rseg, a, b),
-              "tdnnf batchnorm backward statistics") &&
-           ck(kf_bn_train_bwd_apply(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
-                                    net->dz[ib], D),
+    if (!ck(kf_bn_train_bwd_stats(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, drop, D, rseg, a, b),
+            "tdnnf batchnorm backward statistics"))
+        return false;
+    return ck(repair ? kf_bn_train_bwd_apply_repair(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
+                                                    net->dz[ib], D, repair)
+                     : kf_bn_train_bwd_apply(gcur, D, nl.bnt_r, D, T, D, sc, sh, nl.bn_rms, a, b, drop, D, rseg, nl.mask, D,
+                                             net->dz[ib], D),
               "tdnnf batchnorm backward apply");
 }
 // the _rows entries a backward on compact rows needs (weak references, net_internal.h)
@@ -823,7 +848,7 @@ bool BackwardPass::bn_rows_entries() {
 // BatchNorm. One a | b pair serves every site: the chain stream runs them in order. stat_rows < rows:
 // the statistics were those of the first stat_rows rows (the _rows entries).
 bool BackwardPass::bn_site_dz(const void *g, const void *r, int rows, int stat_rows, int H, int F, const float *stat, float rms,
-                              const uint8_t *mask, void *dz_out, const std::string &what) {
+                              const uint8_t *mask, void *dz_out, const std::string &what, const float *repair) {
     if (!g || !r || !stat || !dz_out || g == dz_out || F > net->bnt_w || !kf_bn_train_bwd_stats || !kf_bn_train_bwd_apply ||
         (H > 1 && !kf_bn_block_bwd_stats)) {
         set_err("backward: training-mode BatchNorm of " + what + " got no stored output gradient");
@@ -836,14 +861,18 @@ bool BackwardPass::bn_site_dz(const void *g, const void *r, int rows, int stat_r
         if (H != 1 || !bn_rows_entries()) return false;
         return ck(kf_bn_train_bwd_stats_rows(g, F, r, F, rows, stat_rows, F, sc, sh, rms, nullptr, 0, nullptr, a, b),
                   (what + " batchnorm backward statistics").c_str()) &&
-               ck(kf_bn_train_bwd_apply_rows(g, F, r, F, rows, stat_rows, F, sc, sh, rms, a, b, nullptr, 0, nullptr, mask, F,
-                                             dz_out, F),
+               ck(repair ? kf_bn_train_bwd_apply_rows_repair(g, F, r, F, rows, stat_rows, F, sc, sh, rms, a, b, nullptr, 0, nullptr,
+                                                             mask, F, dz_out, F, repair)
+                         : kf_bn_train_bwd_apply_rows(g, F, r, F, rows, stat_rows, F, sc, sh, rms, a, b, nullptr, 0, nullptr, mask,
+                                                      F, dz_out, F),
                   (what + " batchnorm backward apply").c_str());
     }
     const int rc = H == 1 ? kf_bn_train_bwd_stats(g, F, r, F, rows, F, sc, sh, rms, nullptr, 0, nullptr, a, b)
                           : kf_bn_block_bwd_stats(g, (long long)H * F, r, (long long)H * F, rows, H, F, sc, sh, rms, a, b);
     return ck(rc, (what + " batchnorm backward statistics").c_str()) &&
-           ck(kf_bn_train_bwd_apply(g, F, r, F, rows * H, F, sc, sh, rms, a, b, nullptr, 0, nullptr, mask, F, dz_out, F),
+           ck(repair ? kf_bn_train_bwd_apply_repair(g, F, r, F, rows * H, F, sc, sh, rms, a, b, nullptr, 0, nullptr, mask, F, dz_out,
+                                                    F, repair)
+                     : kf_bn_train_bwd_apply(g, F, r, F, rows * H, F, sc, sh, rms, a, b, nullptr, 0, nullptr, mask, F, dz_out, F),
               (what + " batchnorm backward apply").c_str());
 }
 // the ring slot a governed layer's dz goes to: the one its producer's epilogue left unwritten
@@ -995,7 +1024,8 @@ bool BackwardPass::conv(Step &s) {
     // rows x height-out, then dz into the ring slot, before anything below reads dz
     if (nl.bnt_act) {
         void *slot = bn_site_slot(nl);
-        if (!slot || !bn_site_dz(gcur, nl.bnt_r, s.T, s.T, L.hout, L.fout, nl.bnt_stat, nl.bn_rms, nl.mask, slot, "conv " + L.name))
+        if (!slot || !bn_site_dz(gcur, nl.bnt_r, s.T, s.T, L.hout, L.fout, nl.bnt_stat, nl.bn_rms, nl.mask, slot, "conv " + L.name,
+                                 nl.sr_act ? nl.sr_s : nullptr))
             return false;
     }
     // compact-row conv: the tail window runs first, on the weight-gradient stream beside

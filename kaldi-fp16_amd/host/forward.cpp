@@ -54,19 +54,28 @@ KfEpilogue epi_relu_bn(KfNet *net, NetLayer &nl, int pb, long long ldo) {
 // dense [rows H x F] view. stat = mean | var | scale | shift, acc = count (2) | sum | sumsq.
 // The statistics run over the first stat_rows rows, the apply over all `rows` (a
 // compact layer's rows c < Tc0 against its Tc; everywhere else the two are equal).
+// relu (self-repair, DESIGN §31: count (2) | deriv_sum, or NULL): the same pass counts the active units.
 bool bnt_normalise(const void *r, int stat_rows, int rows, int H, int F, float eps, float rms, float *stat, double *acc,
-                   void *out, const std::string &what) {
+                   void *out, const std::string &what, double *relu = nullptr) {
     // (H = 1, a prefinal layer or a batchnorm-component: wide rows, the column entry's lane map)
-    const int rc = H == 1 ? kf_bn_train_stats(r, F, stat_rows, F, eps, rms, stat, stat + F, stat + 2 * F, stat + 3 * F, acc,
-                                              acc + 2, acc + 2 + F)
-                          : kf_bn_block_stats(r, (long long)H * F, stat_rows, H, F, eps, rms, stat, stat + F, stat + 2 * F,
-                                              stat + 3 * F, acc, acc + 2, acc + 2 + F);
+    int rc;
+    if (relu)
+        rc = H == 1 ? kf_bn_train_stats_relu(r, F, stat_rows, F, eps, rms, stat, stat + F, stat + 2 * F, stat + 3 * F, acc,
+                                             acc + 2, acc + 2 + F, relu, relu + 2)
+                    : kf_bn_block_stats_relu(r, (long long)H * F, stat_rows, H, F, eps, rms, stat, stat + F, stat + 2 * F,
+                                             stat + 3 * F, acc, acc + 2, acc + 2 + F, relu, relu + 2);
+    else
+        rc = H == 1 ? kf_bn_train_stats(r, F, stat_rows, F, eps, rms, stat, stat + F, stat + 2 * F, stat + 3 * F, acc, acc + 2,
+                                        acc + 2 + F)
+                    : kf_bn_block_stats(r, (long long)H * F, stat_rows, H, F, eps, rms, stat, stat + F, stat + 2 * F,
+                                        stat + 3 * F, acc, acc + 2, acc + 2 + F);
     return ck(rc, (what + " batchnorm statistics").c_str()) &&
            ck(kf_bn_train_apply(r, F, rows * H, F, stat + 2 * F, stat + 3 * F, nullptr, 0, nullptr, nullptr, 0, 0.f, out, F),
               (what + " batchnorm apply").c_str());
 }
 bool bnt_conv(NetLayer &nl, int T) {
-    return bnt_normalise(nl.bnt_r, T, T, nl.L.hout, nl.L.fout, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.act, "conv");
+    return bnt_normalise(nl.bnt_r, T, T, nl.L.hout, nl.L.fout, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.act, "conv",
+                         nl.sr_act ? nl.sr_acc : nullptr);
 }
 // the epilogue of a governed conv / prefinal affine: r and the ReLU mask, no scale or shift
 KfEpilogue epi_relu_r(KfNet *net, NetLayer &nl, int pb, long long ldo) {
@@ -229,10 +238,16 @@ bool fwd_tdnnf(KfNet *net, int li, const void *x) {
     Er.out = nl.bnt_r;
     Er.scale = Er.shift = nullptr;
     float *const st = nl.bnt_stat;
-    return ck(kf_gemm_fused(T, dout, kaff, &A2, &B2, &Er), "tdnnf affine") &&
-           ck(kf_bn_train_stats(nl.bnt_r, dout, bnt_stat_rows(net, li), dout, nl.bn_eps, nl.bn_rms, st, st + dout, st + 2 * dout,
-                                st + 3 * dout, nl.bnt_acc, nl.bnt_acc + 2, nl.bnt_acc + 2 + dout),
-              "tdnnf batchnorm statistics") &&
+    // (self-repair, DESIGN §31: the counting entry on the same pass)
+    const int rc_gemm = kf_gemm_fused(T, dout, kaff, &A2, &B2, &Er);
+    if (!ck(rc_gemm, "tdnnf affine")) return false;
+    const int rc_stat =
+        nl.sr_act ? kf_bn_train_stats_relu(nl.bnt_r, dout, bnt_stat_rows(net, li), dout, nl.bn_eps, nl.bn_rms, st, st + dout,
+                                           st + 2 * dout, st + 3 * dout, nl.bnt_acc, nl.bnt_acc + 2, nl.bnt_acc + 2 + dout,
+                                           nl.sr_acc, nl.sr_acc + 2)
+                  : kf_bn_train_stats(nl.bnt_r, dout, bnt_stat_rows(net, li), dout, nl.bn_eps, nl.bn_rms, st, st + dout,
+                                      st + 2 * dout, st + 3 * dout, nl.bnt_acc, nl.bnt_acc + 2, nl.bnt_acc + 2 + dout);
+    return ck(rc_stat, "tdnnf batchnorm statistics") &&
            ck(kf_bn_train_apply(nl.bnt_r, dout, T, dout, st + 2 * dout, st + 3 * dout, E2.drop, E2.ld_drop, E2.row_seg,
                                 E2.resid, E2.ldr, E2.resid_alpha, nl.act, dout),
               "tdnnf batchnorm apply");
@@ -298,7 +313,8 @@ bool fwd_prefinal(KfNet *net, int li, const void *x) {
         E2.ldo = small;
         const int Ts = bnt_stat_rows(net, li);
         return ck(kf_gemm_fused(T, big, din, &A, &B, &Er), "prefinal big") &&
-               bnt_normalise(nl.bnt_r, Ts, T, 1, big, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.aux, "prefinal big") &&
+               bnt_normalise(nl.bnt_r, Ts, T, 1, big, nl.bn_eps, nl.bn_rms, nl.bnt_stat, nl.bnt_acc, nl.aux, "prefinal big",
+                             nl.sr_act ? nl.sr_acc : nullptr) &&
                ck(kf_gemm_fused(T, small, big, &A2, &B2, &E2), "prefinal small") &&
                (!nl.has_bn2 || bnt_normalise(nl.bnt_r2, Ts, T, 1, small, nl.bn2_eps, nl.bn2_rms, nl.bnt_stat2, nl.bnt_acc2,
                                              nl.act, "prefinal small"));
@@ -489,7 +505,7 @@ int forward_impl(KfNet *net, const void *features, int T) {
         const int tc0 = (T - 1) / 3 + 1;
         if (tc0 >= 4 * nt + 16 && tc0 + nt <= net->maxTc) net->rs = RowSet(T, tc0, nt);
     }
-    if (!drop_prepare(net) || !sa_prepare(net) || !bnt_prepare(net)) return -1;
+    if (!drop_prepare(net) || !sa_prepare(net) || !bnt_prepare(net) || !sr_prepare(net, "forward")) return -1;
     for (size_t li = 0; li < net->layers.size(); ++li) {
         NetLayer &nl = net->layers[li];
         const void *x = act_of(net, nl.input);

@@ -13,8 +13,8 @@
 // ---------------------------------------------------------------------------
 namespace {
 
-// "on" as the passes see it: dropout, SpecAugment and training-mode BatchNorm need a layer
-// they apply to besides their switch
+// "on" as the passes see it: dropout, SpecAugment, training-mode BatchNorm and self-repair need a
+// layer they apply to besides their switch
 bool mode_on(const KfNet *net, Mode m) {
     switch (m) {
         case Mode::Fp8: return net->fp8 != 0;
@@ -26,6 +26,7 @@ bool mode_on(const KfNet *net, Mode m) {
         case Mode::BnTrain: return bnt_active(net);
         case Mode::SpecAugment: return sa_active(net);
         case Mode::LossScale: return net->ls_on;
+        case Mode::SelfRepair: return sr_switched(net);
         case Mode::BackwardN:
         case Mode::XentBackward: break;
     }
@@ -44,6 +45,7 @@ const char *phrase(Mode m) {
         case Mode::BnTrain: return "with training-mode BatchNorm on (nnet_set_bn_train)";
         case Mode::SpecAugment: return "with SpecAugment on (nnet_set_spec_augment)";
         case Mode::LossScale: return "with the loss scale on (nnet_set_loss_scale)";
+        case Mode::SelfRepair: return "with ReLU self-repair on (nnet_set_self_repair)";
         case Mode::BackwardN:
         case Mode::XentBackward: break;
     }
@@ -61,6 +63,13 @@ struct Conflict {
 bool bn_rows_subsampled(const KfNet *net) { return net->bnt_rows == KF_BN_ROWS_SUBSAMPLED; }
 // (implicit dz x natural gradient is not here: BackwardPass::begin refuses it, no setter does)
 const Conflict kConflicts[] = {
+    // (self-repair lives in the governed sites' dz, so it is refused where training-mode
+    // BatchNorm is. Its switch counts as on from the moment it is set on a net with a layer it can
+    // govern, training-mode BatchNorm on or not (sr_switched), and its rows stand first: whichever
+    // of the two switches the caller sets second, the text names self-repair.)
+    {Mode::SelfRepair, Mode::Fp8, nullptr, nullptr},
+    {Mode::SelfRepair, Mode::ImplicitDz, nullptr, nullptr},
+    {Mode::SelfRepair, Mode::DataParallel, "the unit statistics would be each rank's own", nullptr},
     {Mode::Fp8, Mode::NaturalGradient, nullptr, nullptr},
     {Mode::Fp8, Mode::Dropout, nullptr, nullptr},
     {Mode::Fp8, Mode::BnTrain, nullptr, nullptr},
@@ -75,6 +84,7 @@ const Conflict kConflicts[] = {
     // backward has block scales of its own)
     {Mode::LossScale, Mode::NaturalGradient, nullptr, nullptr},
     {Mode::LossScale, Mode::Fp8, nullptr, nullptr},
+    {Mode::BackwardN, Mode::SelfRepair, nullptr, nullptr},
     {Mode::BackwardN, Mode::NaturalGradient, nullptr, nullptr},
     {Mode::BackwardN, Mode::Dropout, nullptr, nullptr},
     {Mode::BackwardN, Mode::BnTrain, nullptr, nullptr},

@@ -47,6 +47,11 @@ KF_HIDDEN void set_err(const std::string &s);
 #pragma weak kf_bn_train_bwd_apply_rows
 #pragma weak kf_bn_block_stats
 #pragma weak kf_bn_block_bwd_stats
+#pragma weak kf_bn_train_stats_relu
+#pragma weak kf_bn_block_stats_relu
+#pragma weak kf_relu_repair_vectors
+#pragma weak kf_bn_train_bwd_apply_repair
+#pragma weak kf_bn_train_bwd_apply_rows_repair
 #pragma weak kf_loss_scale_state_bytes
 #pragma weak kf_loss_scale_scratch_bytes
 #pragma weak kf_loss_scale_init
@@ -146,6 +151,16 @@ struct NetLayer {
     void *bnt_r2 = nullptr;
     float *bnt_stat2 = nullptr;
     double *bnt_acc2 = nullptr;
+    // ReLU statistics and self-repair (kf_nnet.h nnet_set_self_repair) of the ReLU that
+    // BatchNorm 0 above governs: the options (xconfig self-repair-*), the accumulators count (2
+    // doubles, the second unused) | deriv_sum [bnt_dim] in double, the last backward's repair vector
+    // s [bnt_dim] fp32, both made when the mode first finds the layer a site, and whether the
+    // current forward counted (the backward then adds s)
+    float sr_scale = 1e-5f;
+    double sr_lower = 0.05, sr_upper = 0.95;
+    double *sr_acc = nullptr;
+    float *sr_s = nullptr;
+    bool sr_act = false;
     // spec-augment-layer (kf_nnet.h nnet_set_spec_augment): the layer's ordinal among such layers
     // (-1: another kind), its options, the row_band [max_T] of its last active forward, and
     // whether the current forward masked (act is then the layer's own buffer, not the alias)
@@ -343,6 +358,15 @@ struct KfNet {
     // be on together; a governed BatchNorm of a compact layer then takes its statistics from the
     // rows c < Tc0 of a compact forward (bnt_stat_rows below)
     int bnt_rows = 0;  // KF_BN_ROWS_ALL
+    // ReLU statistics and self-repair (kf_nnet.h nnet_set_self_repair): the switch, and
+    // the table of the current forward's sites (kf_ops.h KfRepairSite) on the host and on the device,
+    // made again when the sites or an option changed (regularize.cpp sr_prepare)
+    int sr_on = 0;
+    std::vector<int> sr_sites;
+    std::vector<KfRepairSite> sr_tab;
+    void *sr_tab_dev = nullptr;
+    size_t sr_tab_cap = 0;
+    bool sr_dirty = true;
     // data parallel (kf_dp.h): gradient buckets exchanged during the backward
     KfDp *dp = nullptr;
     std::vector<int> dp_after;  // bucket j is issued after backward step dp_after[j]
@@ -484,7 +508,7 @@ inline int list_get(const std::vector<int> &v, int *idx, int n) {
 
 // ---- the modes that cannot all be combined (modes.cpp: the table) ----
 enum class Mode { Fp8, ImplicitDz, RowSubsampling, NaturalGradient, DataParallel, Dropout, BnTrain, SpecAugment,
-                  LossScale,
+                  LossScale, SelfRepair,
                   BackwardN /* nnet_backward_n: never "on", only refused */,
                   XentBackward /* nnet_backward_xent: never "on", only refused */ };
 // may `turning_on` be switched on (or nnet_backward_n / nnet_backward_xent run) beside the modes that are on? false
@@ -508,6 +532,23 @@ inline bool drop_active(const KfNet *net) { return net->drop_on && !net->drop_la
 inline bool sa_active(const KfNet *net) { return net->sa_on && !net->sa_layers.empty(); }
 // training-mode BatchNorm is switched on and the network has a layer it governs (nnet_set_bn_train)
 inline bool bnt_active(const KfNet *net) { return net->bnt_on && !net->bnt_layers.empty(); }
+// a self-repair site (kf_nnet.h nnet_set_self_repair): a governed layer with a ReLU below its BatchNorm 0
+inline bool sr_site_type(LayerType t) {
+    return t == LayerType::TDNNF || t == LayerType::Prefinal || t == LayerType::ConvReluBN;
+}
+// self-repair is switched on and the training-mode BatchNorm sites hold a layer with a ReLU: what
+// the table of mode conflicts calls on (modes.cpp)
+inline bool sr_switched(const KfNet *net) {
+    if (!net->sr_on) return false;
+    for (int li : net->bnt_layers)
+        if (sr_site_type(net->layers[li].L.type)) return true;
+    return false;
+}
+// ... and training-mode BatchNorm is on: the passes count and repair
+inline bool sr_active(const KfNet *net) { return sr_switched(net) && bnt_active(net); }
+// the current forward's sites get their accumulators, repair vectors and table (regularize.cpp);
+// sets every layer's sr_act
+bool sr_prepare(KfNet *net, const char *fn);
 // the length of a layer's BatchNorm statistics (kf_nnet.h nnet_bn_dim): which = 1 is a prefinal
 // layer's second BatchNorm
 inline int bnt_dim(const NetLayer &nl, int which) {

@@ -178,6 +178,9 @@ static bool build_topology(KfNet *net, const char *xconfig_text, int max_frames,
         }
         NetLayer nl;
         nl.L = L;
+        nl.sr_scale = (float)L.self_repair_scale;  // (nnet_set_self_repair; read on tdnnf, prefinal and conv layers)
+        nl.sr_lower = L.self_repair_lower;
+        nl.sr_upper = L.self_repair_upper;
         auto is_seq = [&](int idx) { return idx == -2 || (idx >= 0 && net->layers[idx].per_seq); };
         auto dim_of = [&](int idx) {
             return idx == -2 ? net->ivec_dim : idx >= 0 ? net->layers[idx].L.out_dim : net->feat_dim;

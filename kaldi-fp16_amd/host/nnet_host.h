@@ -70,6 +70,9 @@ struct Layer {  // layers.go:12-120 (specs flattened)
     // of a linear-component (default 0): 0 off, > 0 a fixed scale, < 0 the floating scale
     // (kf_nnet.h nnet_constrain_orthonormal)
     double orthonormal = 0;
+    // self-repair-scale / -lower-threshold / -upper-threshold of the layer's ReLU (tdnnf, prefinal,
+    // conv-relu-batchnorm; Kaldi's xconfig defaults; kf_nnet.h nnet_set_self_repair)
+    double self_repair_scale = 1e-5, self_repair_lower = 0.05, self_repair_upper = 0.95;
 };
 
 bool ParseXConfig(const std::string &text, std::vector<LayerConfig> &out, std::string &err);

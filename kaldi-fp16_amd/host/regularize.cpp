@@ -457,3 +457,181 @@ extern "C" int nnet_bn_commit(KfNet *net) {
     }
     return n;
 }
+
+// ---------------------------------------------------------------------------
+// ReLU unit statistics and self-repair (kf_nnet.h nnet_set_self_repair): the switch,
+// the sites' storage and table, the options and the read-backs. forward.cpp counts through the
+// _relu statistics entries, backward.cpp builds the repair vectors and adds them to the sites' dz.
+// ---------------------------------------------------------------------------
+// the table of net->sr_sites (kf_ops.h KfRepairSite) from the layers' options, on the host and on
+// the device; a blocking copy, so ordered behind every launch that read the old one
+static bool sr_upload(KfNet *net, const char *fn) {
+    const size_t n = net->sr_sites.size();
+    net->sr_tab.clear();
+    for (int li : net->sr_sites) {
+        const NetLayer &nl = net->layers[li];
+        net->sr_tab.push_back(KfRepairSite{nl.sr_acc, nl.sr_acc + 2, nl.sr_s, bnt_dim(nl, 0), nl.sr_scale, nl.sr_lower, nl.sr_upper});
+    }
+    net->sr_dirty = true;  // (until the device holds it)
+    if (n > net->sr_tab_cap) {
+        net->dfree(net->sr_tab_dev);
+        net->sr_tab_cap = 0;
+        if (!(net->sr_tab_dev = net->dalloc(n * sizeof(KfRepairSite)))) {
+            set_err(std::string(fn) + ": alloc self-repair table");
+            return false;
+        }
+        net->sr_tab_cap = n;
+    }
+    if (n && bridge_transfer_int32(net->sr_tab_dev, (const int32_t *)net->sr_tab.data(), n * sizeof(KfRepairSite) / 4)) {
+        set_err(std::string(fn) + ": upload self-repair table");
+        return false;
+    }
+    net->sr_dirty = false;
+    return true;
+}
+
+bool sr_prepare(KfNet *net, const char *fn) {
+    for (NetLayer &nl : net->layers) nl.sr_act = false;
+    if (!sr_active(net)) return true;
+    if (!admit(net, Mode::SelfRepair, fn)) return false;
+    if (!kf_bn_train_stats_relu || !kf_bn_block_stats_relu || !kf_relu_repair_vectors || !kf_bn_train_bwd_apply_repair ||
+        !kf_bn_train_bwd_apply_rows_repair) {
+        set_err(std::string(fn) + ": this build of libkaldi_fp16 has no self-repair kernels");
+        return false;
+    }
+    // the sites of this forward against the table's, without a list of their own: nothing is
+    // allocated on a step that finds the table as it left it
+    auto is_site = [net](int li) { return sr_site_type(net->layers[li].L.type) && net->layers[li].bnt_stat != nullptr; };
+    size_t ns = 0;
+    bool same = !net->sr_dirty;
+    for (int li : net->bnt_layers) {
+        if (!is_site(li)) continue;
+        same = same && ns < net->sr_sites.size() && net->sr_sites[ns] == li;
+        ++ns;
+    }
+    if (!same || ns != net->sr_sites.size()) {
+        net->sr_sites.clear();
+        for (int li : net->bnt_layers)
+            if (is_site(li)) net->sr_sites.push_back(li);
+        // the first time a layer is a site: its accumulators and repair vector
+        for (int li : net->sr_sites) {
+            NetLayer &nl = net->layers[li];
+            if (nl.sr_acc) continue;
+            const size_t D = (size_t)bnt_dim(nl, 0);
+            nl.sr_acc = (double *)net->dalloc((2 + D) * 8);
+            nl.sr_s = (float *)net->dalloc(D * 4);
+            if (!nl.sr_acc || !nl.sr_s) {
+                nl.sr_acc = nullptr;  // (the buffers stay with the net's allocations until it is freed)
+                net->sr_sites.clear();
+                set_err(std::string(fn) + ": alloc self-repair " + nl.L.name);
+                return false;
+            }
+            bridge_gpu_memset(nl.sr_acc, 0, (2 + D) * 8);
+            bridge_gpu_memset(nl.sr_s, 0, D * 4);
+        }
+        if (!sr_upload(net, fn)) return false;
+    }
+    for (int li : net->sr_sites) net->layers[li].sr_act = true;
+    return true;
+}
+
+extern "C" int nnet_set_self_repair(KfNet *net, int on) {
+    if (!on_device(net, "set_self_repair")) return -1;
+    if (!on) {
+        net->sr_on = 0;
+        return 0;
+    }
+    const int old = net->sr_on;
+    net->sr_on = 1;
+    // (where no site exists the switch is accepted and changes nothing, like dropout's)
+    if ((sr_switched(net) && !admit(net, Mode::SelfRepair, "set_self_repair")) || !sr_prepare(net, "set_self_repair")) {
+        net->sr_on = old;
+        return -1;
+    }
+    for (NetLayer &nl : net->layers) nl.sr_act = false;  // (the next forward's to set)
+    return 0;
+}
+
+extern "C" int nnet_self_repair_sites(const KfNet *net, int *idx, int n) {
+    if (!net) return -1;
+    std::vector<int> sites;
+    if (sr_active(net))  // (sr_prepare's rule)
+        for (int li : net->bnt_layers)
+            if (sr_site_type(net->layers[li].L.type) && net->layers[li].bnt_stat) sites.push_back(li);
+    return list_get(sites, idx, n);
+}
+
+static NetLayer *sr_layer(KfNet *net, const char *layer, const char *what) {
+    NetLayer *nl = find_layer(net, layer);
+    if (nl && sr_site_type(nl->L.type)) return nl;
+    set_err(std::string(what) + ": layer " + (layer ? layer : "(null)") + " has no ReLU that self-repair applies to");
+    return nullptr;
+}
+
+extern "C" int nnet_self_repair_opts(const KfNet *net, const char *layer, float *scale, double *lower, double *upper) {
+    NetLayer *nl = sr_layer(const_cast<KfNet *>(net), layer, "self_repair_opts");
+    if (!nl) return -1;
+    if (scale) *scale = nl->sr_scale;
+    if (lower) *lower = nl->sr_lower;
+    if (upper) *upper = nl->sr_upper;
+    return 0;
+}
+
+extern "C" int nnet_set_self_repair_opts(KfNet *net, const char *layer, float scale, double lower, double upper) {
+    NetLayer *nl = sr_layer(net, layer, "set_self_repair_opts");
+    if (!nl) return -1;
+    if (!(scale >= 0.f) || !(lower >= 0.0 && lower < upper && upper <= 1.0)) {
+        set_err("set_self_repair_opts: needs scale >= 0 and 0 <= lower < upper <= 1");
+        return -1;
+    }
+    nl->sr_scale = scale;
+    nl->sr_lower = lower;
+    nl->sr_upper = upper;
+    // a table that holds the layer follows at once: a backward after this call uses the new options
+    const int li = (int)(nl - net->layers.data());
+    if (std::count(net->sr_sites.begin(), net->sr_sites.end(), li) && !sr_upload(net, "set_self_repair_opts")) return -1;
+    return 0;
+}
+
+// the site's storage, or NULL with the error set: the mode never counted in this layer
+static NetLayer *sr_counted(KfNet *net, const char *layer, const char *what) {
+    NetLayer *nl = sr_layer(net, layer, what);
+    if (nl && nl->sr_acc) return nl;
+    if (nl) set_err(std::string(what) + ": self-repair (nnet_set_self_repair) never governed layer " + layer);
+    return nullptr;
+}
+
+// (ordered behind the forward on the current stream, and synchronises; a double read = 4x fp16 count)
+extern "C" int nnet_relu_stats(KfNet *net, const char *layer, double *count, double *value_sum, double *deriv_sum) {
+    if (!on_device(net, "relu_stats")) return -1;
+    NetLayer *nl = sr_counted(net, layer, "relu_stats");
+    if (!nl) return -1;
+    const size_t D = (size_t)bnt_dim(*nl, 0);
+    std::vector<double> h(2 + D);
+    if (bridge_read_fp16((uint16_t *)h.data(), nl->sr_acc, h.size() * 4) ||
+        (value_sum && bridge_read_fp16((uint16_t *)value_sum, nl->bnt_acc + 2, D * 4))) {
+        set_err("relu_stats: read");
+        return -1;
+    }
+    if (count) *count = h[0];
+    if (deriv_sum) std::copy(h.begin() + 2, h.end(), deriv_sum);
+    return 0;
+}
+
+extern "C" int nnet_relu_zero_stats(KfNet *net) {
+    if (!on_device(net, "relu_zero_stats")) return -1;
+    for (NetLayer &nl : net->layers)
+        if (nl.sr_acc) bridge_gpu_memset(nl.sr_acc, 0, (2 + (size_t)bnt_dim(nl, 0)) * 8);
+    return nnet_bn_zero_stats(net);
+}
+
+extern "C" int nnet_self_repair_vector(KfNet *net, const char *layer, float *host) {
+    if (!on_device(net, "self_repair_vector")) return -1;
+    NetLayer *nl = sr_counted(net, layer, "self_repair_vector");
+    if (!nl || !host) return -1;
+    if (bridge_read_fp16((uint16_t *)host, nl->sr_s, 2 * (size_t)bnt_dim(*nl, 0))) {
+        set_err("self_repair_vector: read");
+        return -1;
+    }
+    return 0;
+}

@@ -355,6 +355,28 @@ bool ResolveLayers(const std::vector<LayerConfig> &cfgs, std::vector<Layer> &lay
                 L.orthonormal = v;
             }
         }
+        // self-repair of the layer's ReLU (kf_nnet.h nnet_set_self_repair): a key that is present must
+        // be a number in its range; on any other layer kind the keys do not apply and are not read
+        if (cfg.type == LayerType::TDNNF || cfg.type == LayerType::Prefinal || cfg.type == LayerType::ConvReluBN) {
+            const struct {
+                const char *key;
+                double *v;
+            } keys[] = {{"self-repair-scale", &L.self_repair_scale},
+                        {"self-repair-lower-threshold", &L.self_repair_lower},
+                        {"self-repair-upper-threshold", &L.self_repair_upper}};
+            for (const auto &k : keys) {
+                auto it = cfg.params.find(k.key);
+                if (it == cfg.params.end()) continue;
+                char *end = nullptr;
+                *k.v = strtod(it->second.c_str(), &end);
+                if (it->second.empty() || !end || *end != 0 || !std::isfinite(*k.v))
+                    return fail(std::string(k.key) + " must be a number, got \"" + it->second + "\"");
+            }
+            if (!(L.self_repair_scale >= 0)) return fail("self-repair-scale must be >= 0, got " + cfg.get("self-repair-scale", ""));
+            if (!(L.self_repair_lower >= 0 && L.self_repair_lower < L.self_repair_upper && L.self_repair_upper <= 1))
+                return fail("self-repair thresholds must satisfy 0 <= lower < upper <= 1, got lower=" +
+                            std::to_string(L.self_repair_lower) + " upper=" + std::to_string(L.self_repair_upper));
+        }
         layers.push_back(L);
     }
     return true;

@@ -206,6 +206,14 @@ _sig(nnet, "nnet_bn_batch_stats", _i, _vp, C.c_char_p, _i, _vp, _vp)
 _sig(nnet, "nnet_bn_stats", _i, _vp, C.c_char_p, _i, C.POINTER(C.c_double), _vp, _vp)
 _sig(nnet, "nnet_bn_zero_stats", _i, _vp)
 _sig(nnet, "nnet_bn_commit", _i, _vp)
+# ReLU unit statistics and self-repair (kf_nnet.h nnet_set_self_repair)
+_sig(nnet, "nnet_set_self_repair", _i, _vp, _i)
+_sig(nnet, "nnet_self_repair_sites", _i, _vp, C.POINTER(_i), _i)
+_sig(nnet, "nnet_self_repair_opts", _i, _vp, C.c_char_p, _fp, C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig(nnet, "nnet_set_self_repair_opts", _i, _vp, C.c_char_p, _f, C.c_double, C.c_double)
+_sig(nnet, "nnet_relu_stats", _i, _vp, C.c_char_p, C.POINTER(C.c_double), _vp, _vp)
+_sig(nnet, "nnet_relu_zero_stats", _i, _vp)
+_sig(nnet, "nnet_self_repair_vector", _i, _vp, C.c_char_p, _vp)
 # kf_dp.h (RCCL data parallel)
 _sig(core, "kf_dp_last_error", C.c_char_p)
 _sig(core, "kf_dp_unique_id", _i, C.c_char_p)
@@ -892,6 +900,58 @@ class Network:
             check(-1, "nnet_bn_commit")
         return n
 
+    # ReLU unit statistics and self-repair (kf_nnet.h nnet_set_self_repair) -----
+    def set_self_repair(self, on: bool):
+        """Kaldi's ReLU component statistics and self-repair on / off (default off) for the sites
+        self_repair_sites() names: the ReLUs that training-mode BatchNorm governs. Every forward
+        counts the active units, every backward pushes the pre-activation of a dead unit up and of
+        a saturated one down. Accepted and without effect where no site exists."""
+        check(nnet.nnet_set_self_repair(self.h, int(on)), "nnet_set_self_repair")
+
+    def self_repair_sites(self) -> list:
+        """Names of the layers whose ReLU the switch governs now, in layer order ([] while the
+        switch or training-mode BatchNorm is off)."""
+        n = nnet.nnet_self_repair_sites(self.h, None, 0)
+        idx = (_i * max(n, 1))()
+        nnet.nnet_self_repair_sites(self.h, idx, n)
+        return [self.layers[idx[i]][0] for i in range(n)]
+
+    def set_self_repair_opts(self, layer: str, scale: float = 1e-5, lower: float = 0.05, upper: float = 0.95):
+        """A layer's self-repair-scale and thresholds (the xconfig keys' values until set)."""
+        check(nnet.nnet_set_self_repair_opts(self.h, layer.encode(), float(scale), float(lower), float(upper)),
+              "nnet_set_self_repair_opts")
+
+    def self_repair_opts(self, layer: str) -> dict:
+        """{"scale", "lower", "upper"} of a tdnnf, prefinal or conv layer."""
+        k, lo, hi = _f(), C.c_double(), C.c_double()
+        check(nnet.nnet_self_repair_opts(self.h, layer.encode(), C.byref(k), C.byref(lo), C.byref(hi)),
+              "nnet_self_repair_opts")
+        return {"scale": k.value, "lower": lo.value, "upper": hi.value}
+
+    def relu_stats_raw(self, layer: str):
+        """(count, value_sum, deriv_sum): the float64 accumulators of a site (synchronises)."""
+        d = self._bn_dim(layer, 0)
+        cnt, v, s = C.c_double(), np.empty(d, np.float64), np.empty(d, np.float64)
+        check(nnet.nnet_relu_stats(self.h, layer.encode(), C.byref(cnt), v.ctypes.data, s.ctypes.data), "nnet_relu_stats")
+        return cnt.value, v, s
+
+    def relu_stats(self, layer: str) -> dict:
+        """{"count", "value_avg", "deriv_avg"} of a site: Kaldi's <Count>, <ValueAvg> and <DerivAvg>
+        (zeros while count is 0; synchronises)."""
+        cnt, v, s = self.relu_stats_raw(layer)
+        n = cnt if cnt > 0 else 1.0
+        return {"count": cnt, "value_avg": v / n, "deriv_avg": s / n}
+
+    def relu_zero_stats(self):
+        """Kaldi's ZeroComponentStats: clears the ReLU statistics and the BatchNorm accumulators."""
+        check(nnet.nnet_relu_zero_stats(self.h), "nnet_relu_zero_stats")
+
+    def self_repair_vector(self, layer: str) -> np.ndarray:
+        """The last backward's repair vector s of a site, float32 [D] (synchronises)."""
+        s = np.empty(self._bn_dim(layer, 0), np.float32)
+        check(nnet.nnet_self_repair_vector(self.h, layer.encode(), s.ctypes.data), "nnet_self_repair_vector")
+        return s
+
     def dp_debug_early(self, on: bool):
         """Test hook: issue every gradient bucket before the backward runs (the
         negative control of the overlap tests)."""
@@ -1120,6 +1180,19 @@ _sig(core, "kf_bn_train_bwd_apply", _i, _vp, _ll, _vp, _ll, _i, _i, _vp, _vp, _f
 _sig(core, "kf_bn_train_bwd_stats_rows", _i, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _f, _vp, _ll, _vp, _vp, _vp)
 _sig(core, "kf_bn_train_bwd_apply_rows", _i, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _ll, _vp, _vp,
      _ll, _vp, _ll)
+# ReLU statistics and self-repair (kf_ops.h)
+class KfRepairSite(C.Structure):
+    _fields_ = [("count", _vp), ("deriv", _vp), ("s", _vp), ("D", _i), ("scale", _f), ("lower", C.c_double),
+                ("upper", C.c_double)]
+
+
+_sig(core, "kf_bn_train_stats_relu", _i, _vp, _ll, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig(core, "kf_bn_block_stats_relu", _i, _vp, _ll, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig(core, "kf_relu_repair_vectors", _i, _vp, _vp, _i, _vp)
+_sig(core, "kf_bn_train_bwd_apply_repair", _i, _vp, _ll, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _ll, _vp, _vp, _ll,
+     _vp, _ll, _vp)
+_sig(core, "kf_bn_train_bwd_apply_rows_repair", _i, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _ll, _vp,
+     _vp, _ll, _vp, _ll, _vp)
 _sig(core, "kf_specaug_rows", _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, C.c_uint, C.c_uint64, _ll)
 _sig(core, "kf_specaug_apply", _i, _vp, _ll, _vp, _ll, _ll, _i, _vp)
 _sig(core, "kf_gather_rows", _i, _vp, _vp, _ll, _i, _i, _i)

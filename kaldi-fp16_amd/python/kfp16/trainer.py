@@ -105,6 +105,12 @@ class TrainConfig:
     # the latter is what lets batchnorm_train and row_subsampling be on together. With the default
     # nothing more than before is called.
     batchnorm_train_rows: str = "all"
+    # self_repair: Network.set_self_repair after batchnorm_train: Kaldi's ReLU unit
+    # statistics on every forward and self-repair on every backward, for the ReLUs batchnorm_train
+    # governs, with the xconfig's self-repair-scale (1e-5) and thresholds; the statistics start from
+    # zero. Needs batchnorm_train. EgsTrainer.relu_summary() reads the statistics. False: the
+    # trainer makes exactly the calls it made before.
+    self_repair: bool = False
     # row_subsampling: the row-subsampled step (Network.set_row_subsampling(3) at construction; a
     # topology it does not cover raises there). A step whose subsampling_factor is 3 and whose egs
     # all have their first supervised row at 0 (mod 3) runs the objective on the compact rows; any
@@ -136,6 +142,8 @@ class TrainConfig:
     loss_scale_growth_interval: int = 2000
 
     def __post_init__(self):
+        if self.self_repair and not self.batchnorm_train:
+            raise ValueError("self_repair needs batchnorm_train: its sites are the ReLUs training-mode BatchNorm governs")
         if not (self.loss_scale >= 0.0) or not np.isfinite(self.loss_scale):
             raise ValueError(f"loss_scale {self.loss_scale}: needs a finite value >= 0 (0: off)")
         if self.loss_scale_growth_interval < 1:
@@ -253,11 +261,29 @@ class EgsTrainer:
                 self.net.set_batchnorm_train_sites(self.cfg.batchnorm_train_sites)
             self.net.set_batchnorm_train(True)
             self.net.batchnorm_zero_stats()
+        if self.cfg.self_repair:
+            self.net.set_self_repair(True)
+            self.net.relu_zero_stats()
         if self.cfg.loss_scale > 0:
             self.net.set_loss_scale(True, init_scale=float(self.cfg.loss_scale),
                                     growth_interval=int(self.cfg.loss_scale_growth_interval),
                                     max_scale=max(65536.0, float(self.cfg.loss_scale)))
             self.objective.set_grad_scale(self.net.loss_scale_ptr())
+
+    def relu_summary(self) -> dict:
+        """Per self-repair site, what nnet3-info prints of a ReLU: {"count", "deriv_avg_pct": the 5th,
+        50th and 95th percentile of deriv-avg, "dead", "saturated": the units at or below the site's
+        lower / above its upper threshold, "units"} (synchronises)."""
+        out = {}
+        for name in self.net.self_repair_sites():
+            st, o = self.net.relu_stats(name), self.net.self_repair_opts(name)
+            d = st["deriv_avg"]
+            live = st["count"] > 0
+            out[name] = {"count": st["count"], "units": int(d.size),
+                         "deriv_avg_pct": [float(x) for x in np.percentile(d, [5, 50, 95])],
+                         "dead": int(np.sum(d <= o["lower"])) if live else 0,
+                         "saturated": int(np.sum(d > o["upper"])) if live else 0}
+        return out
 
     def loss_scale_stats(self) -> dict:
         """Network.loss_scale_stats of a trainer with TrainConfig.loss_scale > 0 (synchronises)."""
