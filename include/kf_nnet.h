@@ -210,8 +210,9 @@ int nnet_orthonormal_stats(KfNet *net, float *scale, float *ratio, float *err, i
  * the time splice and, for a component with a bias, an appended column of ones, so that G stacks
  * dW over db), and advances the two preconditioners' states; nnet_sgd and nnet_update then see
  * G^ with no change to either. Preconditioned: the update components of linear, output,
- * tdnnf (.linear and .affine) and prefinal (.affine, .linear) layers on the output's path; conv,
- * attention and per-sequence components keep plain gradients. opts: kf_ng_default_opts gives
+ * tdnnf (.linear and .affine) and prefinal (.affine, .linear) layers on the output's path; conv
+ * (unless nnet_set_natural_gradient_conv below), attention and per-sequence components keep plain
+ * gradients. opts: kf_ng_default_opts gives
  * Kaldi's values (rank_in 20, rank_out 80, update_period 4, num_samples_history 2000, alpha 4).
  * A side's rank is clamped to half its dimension (and to KF_NG_MAX_RANK); a side whose rank
  * would be below 8 is left unpreconditioned. NULL turns the switch off: nnet_backward is then
@@ -220,6 +221,24 @@ int nnet_orthonormal_stats(KfNet *net, float *scale, float *ratio, float *err, i
  * MXFP8 mode, on a net bound to data parallel (and nnet_set_fp8 / nnet_bind_dp fail while it
  * is on), with implicit dz, and in nnet_backward_n. */
 int nnet_set_natural_gradient(KfNet *net, const KfNgOpts *opts);
+/* Natural gradient for the conv-relu-batchnorm-layer components on the chain output's path, on top
+ * of nnet_set_natural_gradient: Kaldi's TimeHeightConvolutionComponent preconditions
+ * the finished parameter derivative G = [dW ; db] itself (kf_ops.h kf_ng_conv_*), first over the
+ * rows of G^T, then over the rows of the unscaled result, after the weight-gradient stream is
+ * joined. A side's rank is clamped as above (half its dimension, KF_NG_MAX_RANK, left alone below
+ * 8); the history is counted in minibatches, eta = 1 - exp(-1 / num_minibatches_history); epsilon,
+ * delta and update_period (and the step count) are those of nnet_set_natural_gradient. opts NULL
+ * with on != 0: nnet_natural_gradient_conv_default_opts. An error while natural gradient is off (so
+ * wherever that is refused); nnet_set_natural_gradient, with options or NULL, switches this off
+ * again. The new preconditioners follow the others in nnet_natural_gradient_count / _stats / _state.
+ * Off (the default): every call is what it was, bit for bit. */
+typedef struct KfNgConvOpts {
+    int rank_in, rank_out;          /* 80, 80 (as recalled from Kaldi's nnet-convolutional-component.cc) */
+    float num_minibatches_history;  /* 4 */
+    float alpha;                    /* 4 */
+} KfNgConvOpts;
+void nnet_natural_gradient_conv_default_opts(KfNgConvOpts *opts);
+int nnet_set_natural_gradient_conv(KfNet *net, int on, const KfNgConvOpts *opts);
 /* the preconditioners (one per preconditioned side of a component), 0 when off */
 int nnet_natural_gradient_count(const KfNet *net);
 /* The report of the last nnet_backward (synchronises) for preconditioners 0 .. n-1: the update

@@ -393,7 +393,8 @@ int kf_orthonormal_constrain(float *w32, void *w16, long long n_params, const Kf
  *   sc  doubles at [s_off, s_off + 2 + Rp): rho, t (the step count), d[Rp] (d_i = 0 for i >= R)
  * and its statistics of one minibatch X [N x D], fp32 at [st_off, st_off + KF_NG_STAT_FLOATS(D, Rp))
  * of the statistics buffer (H = X W^T):
- *   [0] trX = tr(X X^T), [1] N, [2 .. 31] unused
+ *   [0] trX = tr(X X^T), [1] N, [KF_NG_STAT_HISTORY] this preconditioner's own num_samples_history
+ *   (0, as the slots are zeroed at set time: the options' value), [3 .. 31] unused
  *   L  [Rp x Rp] = H^T H           at KF_NG_STAT_L
  *   JT [D x Rp]  = X^T H = J^T     at KF_NG_STAT_JT(Rp)     (updating steps; K = J J^T is formed
  *                                                            from it in double by the state kernel)
@@ -410,6 +411,7 @@ int kf_orthonormal_constrain(float *w32, void *w16, long long n_params, const Kf
  * Tables: pres / comps in host memory (checked, size the launches) and the same tables in
  * device memory (read by the kernels), uploaded once by the caller. */
 #define KF_NG_MAX_RANK 96
+#define KF_NG_STAT_HISTORY 2
 #define KF_NG_STAT_L 32
 #define KF_NG_STAT_JT(Rp) (32 + (long long)(Rp) * (Rp))
 #define KF_NG_STAT_FLOATS(D, Rp) (32 + (long long)(Rp) * (Rp) + (long long)(D) * (Rp))
@@ -463,6 +465,29 @@ int kf_ng_apply(float *g, long long n_grad, const KfNgComp *comps, const KfNgCom
 long long kf_ng_state_scratch_bytes(const KfNgPre *pres, int npre);
 int kf_ng_state(const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const KfNgOpts *opts, int update,
                 float *w32, void *w16, double *sc, const float *stat, void *scratch, float *report);
+
+/* ---- Natural gradient on the parameter side (csrc/natgrad_conv.hip) ----
+ * Kaldi's TimeHeightConvolutionComponent preconditions the finished parameter derivative
+ * G = [dW ; db] [D_in x N] itself, one side after the other, with two of the preconditioners above:
+ *   in side   X = G^T (N rows):    P = W_in G,     trX = |G|_F^2,   L = P P^T,   JT = G P^T
+ *             G1 = G - W_in^T P                                  (gamma_in is withheld)
+ *   out side  X = G1 (D_in rows):  Q = G1 W_out^T, trX = |G1|_F^2,  L = Q^T Q,   JT = G1^T Q
+ *             G^ = gamma_in gamma_out (G1 - Q W_out)
+ * kf_ng_conv_stats leaves g as it is, writes both sides' statistics in the layout above (JT when
+ * update != 0; N = the rows of X; the history slot = num_minibatches_history x those rows, so that
+ * eta = 1 - exp(-1 / num_minibatches_history) whatever the shape) and keeps G1 and Q in scratch;
+ * kf_ng_scales and then kf_ng_conv_apply (gamma from report, G^ into g) and kf_ng_state follow. A
+ * side with pre_in / pre_out < 0 is left alone. P, G1, Q, G^, trX and L run in double on the vector
+ * unit (chunks of 256 rows of G, summed in chunk order), JT on the f32-input MFMA: the in side's in
+ * one chain over N, the out side's in chains of at most 256 rows whose partial tiles are summed in
+ * double. Fixed order throughout, no atomics, no allocation. scratch: kf_ng_conv_scratch_bytes (16-byte aligned device memory). */
+long long kf_ng_conv_scratch_bytes(const KfNgComp *comps, int ncomp, const KfNgPre *pres, int npre);
+int kf_ng_conv_stats(const float *g, long long n_grad, const KfNgComp *comps, const KfNgComp *comps_dev, int ncomp,
+                     const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const float *w32,
+                     float num_minibatches_history, int update, float *stat, void *scratch);
+int kf_ng_conv_apply(float *g, long long n_grad, const KfNgComp *comps, const KfNgComp *comps_dev, int ncomp,
+                     const KfNgPre *pres, const KfNgPre *pres_dev, int npre, const float *w32, const float *report,
+                     const void *scratch);
 
 /* ---- Per-sequence dropout masks (csrc/dropout.hip) ----
  * Kaldi's GeneralDropoutComponent with continuous = true, time-period = 0, block-dim = dim: one

@@ -300,6 +300,7 @@ struct BackwardPass {
     bool ng_stats(int pW, const KfOperand &X, const KfOperand &dY, int T);
     bool ng_side(const KfNgPre &p, const KfOperand &X, bool ones, int T);
     bool ng_finish();
+    bool ngc_finish();
 
     bool begin();
     bool branch_pass(const void *xent_grad, const void *out_grad);
@@ -363,7 +364,15 @@ bool BackwardPass::ng_stats(int pW, const KfOperand &X, const KfOperand &dY, int
 
 // after the weight-gradient stream is joined: the batched scales, apply and state launches
 bool BackwardPass::ng_finish() {
-    if (!net->ng_on || net->ng_comps.empty()) return true;
+    if (!net->ng_on) return true;
+    if (!ngc_finish()) return false;
+    if (net->ng_comps.empty()) {
+        if (net->ngc_on && !net->ngc_comps.empty()) {
+            ++net->ng_t;
+            net->ng_ran = true;
+        }
+        return true;
+    }
     for (size_t i = 0; i < net->ng_comps.size(); ++i)
         if (!net->ng_issued[i]) {
             set_err("natural gradient: a preconditioned component got no weight gradient in this backward");
@@ -382,6 +391,27 @@ bool BackwardPass::ng_finish() {
     ++net->ng_t;
     net->ng_ran = true;
     return true;
+}
+
+// The conv components' parameter-side chain: both sides' statistics from the finished
+// gradient, the scales, G^ and the state, on tables of their own. They touch no element the chain
+// above touches, so which of the two runs first does not show.
+bool BackwardPass::ngc_finish() {
+    if (!net->ngc_on || net->ngc_comps.empty()) return true;
+    const KfNgPre *pres = net->ngc_pres.data(), *pres_dev = (const KfNgPre *)net->ngc_pres_dev;
+    const KfNgComp *comps = net->ngc_comps.data(), *comps_dev = (const KfNgComp *)net->ngc_comps_dev;
+    const int npre = (int)net->ngc_pres.size(), ncomp = (int)net->ngc_comps.size(), upd = net->ng_updating ? 1 : 0;
+    return ck(kf_ng_conv_stats(net->grad, net->nparams, comps, comps_dev, ncomp, pres, pres_dev, npre, net->ngc_w32,
+                               net->ngc_opts.num_minibatches_history, upd, net->ngc_stat, net->ngc_scratch),
+              "natural gradient conv statistics") &&
+           ck(kf_ng_scales(pres, pres_dev, npre, &net->ngc_kopts, net->ngc_sc, net->ngc_stat, net->ngc_report),
+              "natural gradient conv scales") &&
+           ck(kf_ng_conv_apply(net->grad, net->nparams, comps, comps_dev, ncomp, pres, pres_dev, npre, net->ngc_w32,
+                               net->ngc_report, net->ngc_scratch),
+              "natural gradient conv apply") &&
+           ck(kf_ng_state(pres, pres_dev, npre, &net->ngc_kopts, upd, net->ngc_w32, net->ngc_w16, net->ngc_sc, net->ngc_stat,
+                          net->ngc_state_scratch, net->ngc_report),
+              "natural gradient conv state");
 }
 
 bool BackwardPass::begin() {

@@ -14,9 +14,25 @@ static int ng_rank(int want, int dim) {
     return r >= 8 ? r : 0;
 }
 
+// the conv components' tables, state and scratch go back (nnet_set_natural_gradient_conv)
+static void ngc_release(KfNet *net) {
+    net->ngc_on = false;
+    net->ngc_pres.clear();
+    net->ngc_comps.clear();
+    net->ngc_pre_comp.clear();
+    net->ngc_pre_side.clear();
+    void **held[] = {&net->ngc_pres_dev, &net->ngc_comps_dev, (void **)&net->ngc_w32, &net->ngc_w16, (void **)&net->ngc_sc,
+                     (void **)&net->ngc_stat, (void **)&net->ngc_report, &net->ngc_scratch, &net->ngc_state_scratch};
+    for (void **p : held) {
+        net->dfree(*p);
+        *p = nullptr;
+    }
+}
+
 extern "C" int nnet_set_natural_gradient(KfNet *net, const KfNgOpts *opts) {
     kf_take_pending(__func__);
     if (!on_device(net, "set_natural_gradient")) return -1;
+    ngc_release(net);  // the opt-in on top of this switch is set after it, every time
     if (!opts) {
         net->ng_on = false;
         return 0;
@@ -136,8 +152,131 @@ extern "C" int nnet_set_natural_gradient(KfNet *net, const KfNgOpts *opts) {
     return 0;
 }
 
+extern "C" void nnet_natural_gradient_conv_default_opts(KfNgConvOpts *o) {
+    if (!o) return;
+    o->rank_in = 80;
+    o->rank_out = 80;
+    o->num_minibatches_history = 4.f;
+    o->alpha = 4.f;
+}
+
+// Natural gradient on the parameter side of the conv components (kf_nnet.h): tables,
+// state, statistics and scratch of their own; BackwardPass::ng_finish issues the launches
+extern "C" int nnet_set_natural_gradient_conv(KfNet *net, int on, const KfNgConvOpts *opts) {
+    kf_take_pending(__func__);
+    if (!on_device(net, "set_natural_gradient_conv")) return -1;
+    if (!on) {
+        ngc_release(net);
+        return 0;
+    }
+    if (!net->ng_on) {
+        set_err("set_natural_gradient_conv: natural gradient is off (nnet_set_natural_gradient comes first)");
+        return -1;
+    }
+    if (!kf_ng_conv_scratch_bytes || !kf_ng_conv_stats || !kf_ng_conv_apply) {
+        set_err("set_natural_gradient_conv: this build of libkaldi_fp16 has no kf_ng_conv_* kernels");
+        return -1;
+    }
+    KfNgConvOpts o;
+    nnet_natural_gradient_conv_default_opts(&o);
+    if (opts) o = *opts;
+    if (o.rank_in < 0 || o.rank_out < 0 || !(o.num_minibatches_history > 0.f) || !(o.alpha >= 0.f)) {
+        set_err("set_natural_gradient_conv: bad options");
+        return -1;
+    }
+    ngc_release(net);
+    net->ngc_opts = o;
+    net->ngc_kopts = net->ng_opts;
+    net->ngc_kopts.rank_in = o.rank_in;
+    net->ngc_kopts.rank_out = o.rank_out;
+    net->ngc_kopts.alpha = o.alpha;
+    long long w = 0, h = 0, s = 0, st = 0;
+    auto add_pre = [&](int D, int R, int comp, int side) {
+        const int Rp = ng_rp(R);
+        net->ngc_pres.push_back(KfNgPre{D, R, w, h, s, st});
+        net->ngc_pre_comp.push_back(comp);
+        net->ngc_pre_side.push_back(side);
+        w += (long long)Rp * D;
+        h += KF_NG_W16_HALFS(D, Rp);
+        s += 2 + Rp;
+        st += KF_NG_STAT_FLOATS(D, Rp);
+        return (int)net->ngc_pres.size() - 1;
+    };
+    for (const NetLayer &nl : net->layers) {
+        if (nl.L.type != LayerType::ConvReluBN || nl.pW < 0) continue;
+        const ParamRef &p = net->params[nl.pW];
+        bool off = false;  // no gradient: nnet_backward zeroes it
+        for (const auto &r : net->offpath) off = off || (p.off >= r.first && p.off < r.first + r.second);
+        if (off) continue;
+        int ci = -1;
+        for (size_t c = 0; c < net->comps.size(); ++c)
+            if (nl.pW >= net->comps[c].first && nl.pW < net->comps[c].first + net->comps[c].count) ci = (int)c;
+        const int din = p.rows + (nl.pb >= 0 ? 1 : 0);
+        const int rin = ng_rank(o.rank_in, din), rout = ng_rank(o.rank_out, p.cols);
+        if (!rin && !rout) continue;
+        KfNgComp c{p.off, nl.pb >= 0 ? net->params[nl.pb].off : -1, p.rows, p.cols, -1, -1};
+        if (rin) c.pre_in = add_pre(din, rin, ci, 0);
+        if (rout) c.pre_out = add_pre(p.cols, rout, ci, 1);
+        net->ngc_comps.push_back(c);
+    }
+    if (net->ngc_comps.empty()) {
+        net->ngc_on = true;
+        return 0;
+    }
+    const int npre = (int)net->ngc_pres.size(), ncomp = (int)net->ngc_comps.size();
+    const long long ab = kf_ng_conv_scratch_bytes(net->ngc_comps.data(), ncomp, net->ngc_pres.data(), npre);
+    const long long sb = kf_ng_state_scratch_bytes(net->ngc_pres.data(), npre);
+    if (ab < 0 || sb < 0) {
+        set_err(std::string("set_natural_gradient_conv: ") + (kf_last_error() ? kf_last_error() : "scratch size"));
+        return -1;
+    }
+    net->ngc_pres_dev = net->dalloc(npre * sizeof(KfNgPre));
+    net->ngc_comps_dev = net->dalloc(ncomp * sizeof(KfNgComp));
+    net->ngc_w32 = (float *)net->dalloc((size_t)w * 4);
+    net->ngc_w16 = net->dalloc((size_t)h * 2);
+    net->ngc_sc = (double *)net->dalloc((size_t)s * 8);
+    net->ngc_stat = (float *)net->dalloc((size_t)st * 4);
+    net->ngc_report = (float *)net->dalloc((size_t)npre * KF_NG_REPORT * 4);
+    net->ngc_scratch = net->dalloc((size_t)ab);
+    net->ngc_state_scratch = net->dalloc((size_t)sb);
+    if (!net->ngc_pres_dev || !net->ngc_comps_dev || !net->ngc_w32 || !net->ngc_w16 || !net->ngc_sc || !net->ngc_stat ||
+        !net->ngc_report || !net->ngc_scratch || !net->ngc_state_scratch ||
+        bridge_transfer_int32(net->ngc_pres_dev, (const int32_t *)net->ngc_pres.data(), npre * sizeof(KfNgPre) / 4) ||
+        bridge_transfer_int32(net->ngc_comps_dev, (const int32_t *)net->ngc_comps.data(), ncomp * sizeof(KfNgComp) / 4)) {
+        set_err("set_natural_gradient_conv: alloc / upload of the tables");
+        return -1;
+    }
+    bridge_gpu_memset(net->ngc_stat, 0, (size_t)st * 4);
+    bridge_gpu_memset(net->ngc_report, 0, (size_t)npre * KF_NG_REPORT * 4);
+    if (!ck(kf_ng_init(net->ngc_pres.data(), (const KfNgPre *)net->ngc_pres_dev, npre, &net->ngc_kopts, net->ngc_w32,
+                       net->ngc_w16, net->ngc_sc),
+            "set_natural_gradient_conv"))
+        return -1;
+    // (the updating schedule stays nnet_set_natural_gradient's step count; set right after it, as
+    // the trainer does, the two count together)
+    net->ng_ran = false;
+    net->ngc_on = true;
+    return 0;
+}
+
+// the tables and buffers preconditioner idx lives in: the conv components' follow the others
+namespace {
+struct NgWhere {
+    const KfNgPre *p;
+    int comp, side;
+    const float *w32, *report;
+    const double *sc;
+};
+NgWhere ng_where(const KfNet *net, int idx) {
+    const int n0 = (int)net->ng_pres.size();
+    if (idx < n0) return {&net->ng_pres[idx], net->ng_pre_comp[idx], net->ng_pre_side[idx], net->ng_w32, net->ng_report, net->ng_sc};
+    idx -= n0;
+    return {&net->ngc_pres[idx], net->ngc_pre_comp[idx], net->ngc_pre_side[idx], net->ngc_w32, net->ngc_report, net->ngc_sc};
+}
+}  // namespace
+
 extern "C" int nnet_natural_gradient_count(const KfNet *net) {
-    return net && net->ng_on ? (int)net->ng_pres.size() : 0;
+    return net && net->ng_on ? (int)net->ng_pres.size() + (net->ngc_on ? (int)net->ngc_pres.size() : 0) : 0;
 }
 
 extern "C" int nnet_natural_gradient_stats(KfNet *net, int *component, int *side, float *report, int n) {
@@ -151,13 +290,16 @@ extern "C" int nnet_natural_gradient_stats(KfNet *net, int *component, int *side
     }
     // D2H through the bridge, ordered behind the backward on the current stream
     std::vector<float> rep((size_t)npre * KF_NG_REPORT);
-    if (npre && bridge_read_fp16((uint16_t *)rep.data(), net->ng_report, rep.size() * 2)) {  // (fp32 = 2x fp16 count)
+    const size_t n0 = net->ng_pres.size() * KF_NG_REPORT;  // (fp32 = 2x fp16 count)
+    if ((n0 && bridge_read_fp16((uint16_t *)rep.data(), net->ng_report, n0 * 2)) ||
+        (rep.size() > n0 && bridge_read_fp16((uint16_t *)(rep.data() + n0), net->ngc_report, (rep.size() - n0) * 2))) {
         set_err("natural_gradient_stats: read");
         return -1;
     }
     for (int i = 0; i < n; ++i) {
-        if (component) component[i] = net->ng_pre_comp[i];
-        if (side) side[i] = net->ng_pre_side[i];
+        const NgWhere at = ng_where(net, i);
+        if (component) component[i] = at.comp;
+        if (side) side[i] = at.side;
         if (report) memcpy(report + (size_t)i * KF_NG_REPORT, rep.data() + (size_t)i * KF_NG_REPORT, KF_NG_REPORT * 4);
     }
     return 0;
@@ -166,19 +308,20 @@ extern "C" int nnet_natural_gradient_stats(KfNet *net, int *component, int *side
 extern "C" int nnet_natural_gradient_state(KfNet *net, int idx, int *component, int *side, int *dim, int *rank,
                                            float *W, double *d, double *rho, double *t) {
     if (!on_device(net, "natural_gradient_state")) return -1;
-    if (!net->ng_on || idx < 0 || idx >= (int)net->ng_pres.size()) {
+    if (!net->ng_on || idx < 0 || idx >= nnet_natural_gradient_count(net)) {
         set_err("natural_gradient_state: natural gradient is off, or no such preconditioner");
         return -1;
     }
-    const KfNgPre &p = net->ng_pres[idx];
-    if (component) *component = net->ng_pre_comp[idx];
-    if (side) *side = net->ng_pre_side[idx];
+    const NgWhere at = ng_where(net, idx);
+    const KfNgPre &p = *at.p;
+    if (component) *component = at.comp;
+    if (side) *side = at.side;
     if (dim) *dim = p.D;
     if (rank) *rank = p.R;
     std::vector<double> sc(2 + p.R);
     // (fp32 / double reads = 2x / 4x the fp16 count, as nnet_update_stats)
-    if ((W && bridge_read_fp16((uint16_t *)W, net->ng_w32 + p.w_off, (size_t)p.R * p.D * 2)) ||
-        bridge_read_fp16((uint16_t *)sc.data(), net->ng_sc + p.s_off, sc.size() * 4)) {
+    if ((W && bridge_read_fp16((uint16_t *)W, at.w32 + p.w_off, (size_t)p.R * p.D * 2)) ||
+        bridge_read_fp16((uint16_t *)sc.data(), at.sc + p.s_off, sc.size() * 4)) {
         set_err("natural_gradient_state: read");
         return -1;
     }

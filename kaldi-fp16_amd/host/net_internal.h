@@ -35,6 +35,9 @@ KF_HIDDEN void set_err(const std::string &s);
 #pragma weak kf_ng_scales
 #pragma weak kf_ng_apply
 #pragma weak kf_ng_state
+#pragma weak kf_ng_conv_scratch_bytes
+#pragma weak kf_ng_conv_stats
+#pragma weak kf_ng_conv_apply
 #pragma weak kf_dropout_masks
 #pragma weak kf_row_seg
 #pragma weak kf_specaug_rows
@@ -327,6 +330,19 @@ struct KfNet {
     long long ng_t = 0;      // steps so far: t < 10 or t % update_period == 0 updates the state
     bool ng_updating = false;  // this backward's steps
     bool ng_ran = false;     // ng_report holds a backward's report
+    // ... and on the parameter side of the conv components (nnet_set_natural_gradient_conv):
+    // tables and state of their own, listed after the ones above; the step count and the updating
+    // schedule are ng_t's
+    bool ngc_on = false;
+    KfNgConvOpts ngc_opts{};
+    KfNgOpts ngc_kopts{};  // ng_opts with the conv options' alpha: what the kernels of these tables get
+    std::vector<KfNgPre> ngc_pres;
+    std::vector<KfNgComp> ngc_comps;
+    std::vector<int> ngc_pre_comp, ngc_pre_side;
+    void *ngc_pres_dev = nullptr, *ngc_comps_dev = nullptr, *ngc_w16 = nullptr;
+    void *ngc_scratch = nullptr, *ngc_state_scratch = nullptr;
+    float *ngc_w32 = nullptr, *ngc_stat = nullptr, *ngc_report = nullptr;
+    double *ngc_sc = nullptr;
     // per-sequence dropout (kf_nnet.h nnet_set_dropout): the layers with a component,
     // the switch, the generator's key and step, the sequence boundaries nnet_set_sequences gave
     // (host copy; seq_off holds them on the device), the row -> sequence maps of the current

@@ -160,6 +160,8 @@ _sig(nnet, "nnet_constrain_orthonormal", _i, _vp)
 _sig(nnet, "nnet_orthonormal_stats", _i, _vp, _vp, _vp, _vp, _i)
 _sig(nnet, "nnet_set_natural_gradient", _i, _vp, _vp)
 _sig(nnet, "nnet_natural_gradient_count", _i, _vp)
+_sig(nnet, "nnet_natural_gradient_conv_default_opts", None, _vp)
+_sig(nnet, "nnet_set_natural_gradient_conv", _i, _vp, _i, _vp)
 _sig(nnet, "nnet_natural_gradient_stats", _i, _vp, _vp, _vp, _vp, _i)
 _sig(nnet, "nnet_natural_gradient_state", _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig(nnet, "nnet_bind_grad_buffer", _i, _vp, _vp)
@@ -640,12 +642,18 @@ class Network:
         return dict(names=names, scale=s, ratio=r, err=e)
 
     # Natural-gradient preconditioning (kf_nnet.h nnet_set_natural_gradient) ----
-    def set_natural_gradient(self, on: bool = True, **opts):
+    def set_natural_gradient(self, on: bool = True, conv: bool = False, conv_opts: dict = None, **opts):
         """Kaldi's NG-SGD on the weight gradients of the linear, output, tdnnf and prefinal
         components: backward() then leaves the preconditioned gradient for sgd() / update().
         opts override kf_ng_default_opts (rank_in 20, rank_out 80, update_period 4,
         num_samples_history 2000, alpha 4); every call with on=True starts the preconditioners
-        from their default initial state. on=False: the plain gradients, as before."""
+        from their default initial state. on=False: the plain gradients, as before.
+        conv=True adds the conv-relu-batchnorm-layer components, preconditioned on the parameter
+        side as Kaldi's TimeHeightConvolutionComponent does (kf_nnet.h
+        nnet_set_natural_gradient_conv); conv_opts override its defaults (rank_in 80, rank_out 80,
+        num_minibatches_history 4, alpha 4). conv=False: exactly the calls made without it."""
+        if conv and not on:
+            raise ValueError("set_natural_gradient: conv=True needs on=True")
         if not on:
             check(nnet.nnet_set_natural_gradient(self.h, None), "nnet_set_natural_gradient")
             return
@@ -656,6 +664,14 @@ class Network:
                 raise TypeError(f"set_natural_gradient: unknown option {k}")
             setattr(o, k, v)
         check(nnet.nnet_set_natural_gradient(self.h, C.byref(o)), "nnet_set_natural_gradient")
+        if conv:
+            co = KfNgConvOpts()
+            nnet.nnet_natural_gradient_conv_default_opts(C.byref(co))
+            for k, v in (conv_opts or {}).items():
+                if k not in dict(KfNgConvOpts._fields_):
+                    raise TypeError(f"set_natural_gradient: unknown conv option {k}")
+                setattr(co, k, v)
+            check(nnet.nnet_set_natural_gradient_conv(self.h, 1, C.byref(co)), "nnet_set_natural_gradient_conv")
 
     def natural_gradient_stats(self) -> list:
         """The last backward's report (synchronises), one dict per preconditioned side of a
@@ -1129,6 +1145,10 @@ class KfNgOpts(C.Structure):
                 ("alpha", _f), ("epsilon", _f), ("delta", _f)]
 
 
+class KfNgConvOpts(C.Structure):  # kf_nnet.h
+    _fields_ = [("rank_in", _i), ("rank_out", _i), ("num_minibatches_history", _f), ("alpha", _f)]
+
+
 class KfNgPre(C.Structure):
     _fields_ = [("D", _i), ("R", _i), ("w_off", _ll), ("h_off", _ll), ("s_off", _ll), ("st_off", _ll)]
 
@@ -1164,6 +1184,9 @@ _sig(core, "kf_ng_apply_scratch_bytes", _ll, _vp, _i, _vp, _i)
 _sig(core, "kf_ng_apply", _i, _vp, _ll, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp)
 _sig(core, "kf_ng_state_scratch_bytes", _ll, _vp, _i)
 _sig(core, "kf_ng_state", _i, _vp, _vp, _i, C.POINTER(KfNgOpts), _i, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig(core, "kf_ng_conv_scratch_bytes", _ll, _vp, _i, _vp, _i)
+_sig(core, "kf_ng_conv_stats", _i, _vp, _ll, _vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _vp, _vp)
+_sig(core, "kf_ng_conv_apply", _i, _vp, _ll, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp)
 class KfDropLayer(C.Structure):
     _fields_ = [("mask", _vp), ("ld", _ll), ("dim", _i), ("ordinal", _i), ("p", _f), ("reserved", _i)]
 

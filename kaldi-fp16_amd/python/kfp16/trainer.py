@@ -77,6 +77,10 @@ class TrainConfig:
     # the backward leaves the preconditioned weight gradients of the linear, output, tdnnf and
     # prefinal components for step 4, with either update. False: plain gradients, as before.
     natural_gradient: bool = False
+    # natural_gradient_conv: with natural_gradient, also the conv-relu-batchnorm-layer components, on
+    # the parameter side as Kaldi's TimeHeightConvolutionComponent does it
+    # (Network.set_natural_gradient(True, conv=True)). False: exactly the calls made without it.
+    natural_gradient_conv: bool = False
     # dropout_schedule: Kaldi's --trainer.dropout-schedule, e.g. '0,0@0.20,0.5@0.50,0': the
     # proportion of every layer with a dropout component (xconfig dropout-proportion >= 0) as a
     # piecewise-linear function of the fraction of data processed (dropout_proportion below), set
@@ -148,6 +152,8 @@ class TrainConfig:
             raise ValueError(f"loss_scale {self.loss_scale}: needs a finite value >= 0 (0: off)")
         if self.loss_scale_growth_interval < 1:
             raise ValueError(f"loss_scale_growth_interval {self.loss_scale_growth_interval}: needs >= 1")
+        if self.natural_gradient_conv and not self.natural_gradient:
+            raise ValueError("natural_gradient_conv needs natural_gradient")
         if self.loss_scale > 0 and self.natural_gradient:
             raise ValueError("loss_scale is not supported with natural_gradient: the preconditioner's Fisher "
                              "state is not scale-equivariant across a change of the scale")
@@ -244,7 +250,7 @@ class EgsTrainer:
         else:
             self.opts = self.cfg.opts
         if self.cfg.natural_gradient:
-            self.net.set_natural_gradient(True)
+            self.net.set_natural_gradient(True, conv=self.cfg.natural_gradient_conv)
         if self.cfg.dropout_schedule:
             parse_dropout_schedule(self.cfg.dropout_schedule)  # a malformed schedule fails here
             # (each data-parallel rank its own masks: the rank folded into the seed)
