@@ -167,6 +167,88 @@ def test_plan_rules():
         dp.plan([0], [11], 10, 1)
 
 
+def _plan_restated(lo, hi, total, bucket_elems, max_buckets):
+    """include/kf_dp.h's comment on kf_dp_plan, restated: groups in visiting order, empty ones
+    skipped; a cut after group i when [lo[i], top) holds bucket_elems values and one bucket is
+    still left for the rest; [0, top) after the last group (a group at offset 0 therefore never
+    cuts: test_plan_rules' first line); a group reaching above top: one bucket after the backward"""
+    n, top, out = len(lo), total, []
+    for i in range(n):
+        if lo[i] == hi[i]:
+            continue
+        if hi[i] > top:
+            return [(n, 0, total)], True
+        if lo[i] > 0 and top - lo[i] >= bucket_elems and len(out) + 1 < max_buckets:
+            out.append((i, lo[i], top))
+            top = lo[i]
+    if top > 0 or not out:
+        out.append((n, 0, top))
+    return out, False
+
+
+def _random_groups(rng, kind):
+    """(lo, hi, total): `kind` 0 descending groups that tile a range below total with empty groups
+    among them, 1 the same shuffled, 2 the same with one group moved up across the ones before it
+    (it reaches above what has been exchanged), 3 arbitrary intervals"""
+    total = int(rng.integers(1, 3000))
+    n = int(rng.integers(1, 14))
+    if kind == 3:
+        a, b = rng.integers(0, total + 1, n), rng.integers(0, total + 1, n)
+        return np.minimum(a, b).tolist(), np.maximum(a, b).tolist(), total
+    cuts = np.sort(rng.integers(0, total + 1, n + 1))[::-1]      # equal cuts: empty groups
+    if rng.integers(2):
+        cuts[-1] = 0                                               # the last group starts the buffer
+    lo, hi = cuts[1:].tolist(), cuts[:-1].tolist()
+    for i in rng.integers(0, n, int(rng.integers(0, 3))):        # more empty groups, anywhere in range
+        lo[i] = hi[i] = int(rng.integers(0, total + 1))
+    if kind == 1:
+        o = rng.permutation(n)
+        lo, hi = [lo[i] for i in o], [hi[i] for i in o]
+    if kind == 2 and n > 1:
+        i = int(rng.integers(0, n - 1))
+        lo.append(lo.pop(i))
+        hi.append(hi.pop(i))
+    return lo, hi, total
+
+
+def test_plan_properties():
+    """kf_dp_plan on 600 seeded random group lists, each at max_buckets 1, 2 and 256, against the
+    restated rule and against what the gates of nnet_backward rely on: the buckets tile
+    [0, total), no bucket is issued before the last group that overlaps it (BackwardPass::step
+    calls dp_issue(done) after step `done`'s launches, and dp_issue sends the buckets with
+    after_step <= done: a group i overlapping bucket j needs i <= after_step[j]), the issue order
+    is that of after_step, and at most max_buckets buckets are written."""
+    from kfp16 import dp
+    rng = np.random.default_rng(20261126)
+    seen = dict(fallback=0, cuts=0, limited=0, empty_groups=0)
+    for case in range(600):
+        lo, hi, total = _random_groups(rng, case % 4)
+        span = max(hi) - min(lo)
+        bucket = int(rng.choice([0, 1, max(1, span // 8), max(1, span // 3), total + 1]))
+        n = len(lo)
+        seen["empty_groups"] += any(a == b for a, b in zip(lo, hi))
+        for max_buckets in (1, 2, 256):
+            plan = dp.plan(lo, hi, total, bucket, max_buckets)
+            what = (case, lo, hi, total, bucket, max_buckets, plan)
+            want, fell_back = _plan_restated(lo, hi, total, bucket, max_buckets)
+            assert plan == want, what
+            assert 1 <= len(plan) <= max_buckets, what
+            assert dp.covers_exactly(plan, total), what
+            assert all(0 <= b <= e <= total for _, b, e in plan), what
+            after = [a for a, _, _ in plan]
+            assert after == sorted(after) and all(0 <= a <= n for a in after), what
+            for a, b, e in plan:
+                late = [i for i in range(n) if lo[i] < hi[i] and lo[i] < e and b < hi[i] and i > a]
+                assert not late, (what, "groups written after their bucket was issued", late)
+            if max_buckets == 256:
+                seen["cuts"] += len(plan) > 2
+                seen["fallback"] += fell_back
+            if max_buckets == 2:
+                seen["limited"] += len(dp.plan(lo, hi, total, bucket, 256)) > 2
+    # the generator reached what it is for
+    assert min(seen.values()) >= 20, seen
+
+
 @pytest.mark.timeout(300)
 def test_bench_launcher_two_ranks_cpu():
     """bench.py --gpus 2 without WORLD_SIZE starts two ranks itself (the driver's
