@@ -65,6 +65,24 @@ typedef struct {
 KfDenGraph *kf_den_graph_create(int num_states, int num_pdfs, int num_transitions,
                                 const int32_t *src, const int32_t *dst, const int32_t *pdf0,
                                 const float *tp, int start_state, const float *initial_probs);
+/* Where the denominator keeps its alpha' / beta rows.
+ *   KF_DEN_ROWS_LDS     kf_den_graph_create: the LDS-resident kernels, with its refusals
+ *                       (num_pdfs <= 4096, num_states < 8192, ~12 S + 14 P bytes of LDS).
+ *   KF_DEN_ROWS_GLOBAL  rows in device memory, one launch per frame and direction: any graph with
+ *                       1 <= num_states, num_pdfs <= 65535 and num_transitions >= 1, small ones
+ *                       too. kf_chain_create sizes a workspace from (S, P, max_seqs, max_frames)
+ *                       and names its byte count when the allocation fails. Every kf_chain_* entry
+ *                       works on such a graph; the exchange diagnostics (kf_chain_debug_spin_limit,
+ *                       _exchange_sys, _den_pairs, kf_chain_trace) have no effect and
+ *                       kf_chain_debug_census reports zeros. A compute replays bit for bit; the two
+ *                       paths' summation orders differ, so they agree to rounding only.
+ *   KF_DEN_ROWS_AUTO    LDS where kf_den_graph_create accepts the graph, GLOBAL otherwise. */
+enum { KF_DEN_ROWS_LDS = 0, KF_DEN_ROWS_GLOBAL = 1, KF_DEN_ROWS_AUTO = 2 };
+KfDenGraph *kf_den_graph_create_rows(int num_states, int num_pdfs, int num_transitions,
+                                     const int32_t *src, const int32_t *dst, const int32_t *pdf0,
+                                     const float *tp, int start_state, const float *initial_probs,
+                                     int rows);
+int kf_den_graph_rows(const KfDenGraph *g);   /* KF_DEN_ROWS_LDS or KF_DEN_ROWS_GLOBAL, resolved */
 int kf_den_graph_initial_probs(const KfDenGraph *g, float *out /* host [S] */);
 void kf_den_graph_free(KfDenGraph *g);
 

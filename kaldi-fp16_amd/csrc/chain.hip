@@ -8,9 +8,12 @@
 //   chain_tables.cpp  host-side table builders and graph validation, no HIP
 //   chain_num.hip     numerator: k_num_fb + k_num_post (FST in LDS), k_logfb (any FST, ABI)
 //   chain_den.hip     denominator: k_den_fwd, k_den_fb, k_den_post, the exchange
+//   chain_den_global.hip  denominator of the graphs those refuse: state rows in device memory,
+//                     one launch per frame (kf_den_graph_create_rows)
 //   chain_xent.hip    the xent output's derivative and objective: k_chain_xent (kf_chain_xent)
 //   chain_abi.hip     the reference ABIs chain.h, chain_backward_api.h, chain_den.h
 #include "chain_denom.h"
+#include "chain_den_global.h"
 #include "chain_num.h"
 #include "chain_xent.h"
 #include "kf_prof.h"
@@ -24,12 +27,15 @@ extern "C" const char *kf_chain_last_error(void) { return kfc_err_.get(); }
 extern "C" void kf_chain_clear_error(void) { kfc_err_.clear(); }
 
 struct KfDenGraph {
-    DenTables *t = nullptr;
+    DenTables *t = nullptr;   // KF_DEN_ROWS_LDS
+    DgTables *gt = nullptr;   // KF_DEN_ROWS_GLOBAL
+    int S = 0, P = 0;
     int num_arcs = 0;
     std::vector<float> init;
     float *d_init = nullptr;
     ~KfDenGraph() {
         delete t;
+        delete gt;
         if (d_init) hipFree(d_init);
     }
 };
@@ -111,6 +117,8 @@ struct KfChain {
     std::vector<LogFstDev> host_desc;
     size_t num_lds = 0;           // dynamic LDS of k_num_fb, 0 = use k_logfb
     float *den_out = nullptr;     // [max_seqs][2]
+    float *dg_ws = nullptr;       // workspace of a global-rows graph (DgWork), else null
+    DgWork dg_work{};
     hipStream_t side = nullptr;   // numerator stream (overlaps the den forward)
     hipEvent_t ev_in = nullptr, ev_num = nullptr;
     DenXBuf xbuf;
@@ -131,6 +139,7 @@ struct KfChain {
         if (ev_in) hipEventDestroy(ev_in);
         if (ev_num) hipEventDestroy(ev_num);
         if (den_out) hipFree(den_out);
+        if (dg_ws) hipFree(dg_ws);
         for (void *p : {(void *)alpha_store, (void *)beta_store, (void *)asum_store, (void *)bsum_store,
                         (void *)stats, (void *)num_ab,
                         (void *)num_post, (void *)d_desc, (void *)d_num_total})
@@ -154,6 +163,8 @@ extern "C" KfDenGraph *kf_den_graph_create(int S, int P, int A, const int32_t *s
     }
     auto *g = new KfDenGraph();
     g->t = t;
+    g->S = S;
+    g->P = P;
     g->num_arcs = A;
     g->init.resize(S);
     if (initial_probs)
@@ -175,6 +186,46 @@ extern "C" KfDenGraph *kf_den_graph_create(int S, int P, int A, const int32_t *s
         return nullptr;
     }
     return g;
+}
+
+extern "C" KfDenGraph *kf_den_graph_create_rows(int S, int P, int A, const int32_t *src, const int32_t *dst,
+                                                const int32_t *pdf0, const float *tp, int start_state,
+                                                const float *initial_probs, int rows) {
+    if (rows != KF_DEN_ROWS_LDS && rows != KF_DEN_ROWS_GLOBAL && rows != KF_DEN_ROWS_AUTO) {
+        kfc_set_error("kf_den_graph_create_rows: rows %d is none of KF_DEN_ROWS_LDS, _GLOBAL, _AUTO", rows);
+        return nullptr;
+    }
+    if (rows != KF_DEN_ROWS_GLOBAL) {
+        KfDenGraph *g = kf_den_graph_create(S, P, A, src, dst, pdf0, tp, start_state, initial_probs);
+        if (g || rows == KF_DEN_ROWS_LDS) return g;
+        // AUTO: whatever the LDS path refuses goes to the global path, whose own validation
+        // reports a malformed graph
+    }
+    const char *why = nullptr;
+    if (!src || !dst || !pdf0 || !tp || start_state < 0 || start_state >= S) {
+        kfc_set_error("kf_den_graph_create: invalid arguments");
+        return nullptr;
+    }
+    auto *g = new KfDenGraph();
+    g->S = S;
+    g->P = P;
+    g->num_arcs = A;
+    g->init.resize(S);
+    if (initial_probs)
+        memcpy(g->init.data(), initial_probs, (size_t)S * 4);
+    else if (A > 0)
+        compute_initial_probs(S, A, src, dst, tp, start_state, g->init.data());
+    g->gt = make_dg_tables(S, P, A, src, dst, pdf0, tp, g->init.data(), &why);
+    if (!g->gt) {
+        delete g;
+        kfc_set_error("kf_den_graph_create: %s", why);
+        return nullptr;
+    }
+    kfc_err_.clear();  // AUTO: the LDS path's refusal is not this call's error
+    return g;
+}
+extern "C" int kf_den_graph_rows(const KfDenGraph *g) {
+    return g && g->gt ? KF_DEN_ROWS_GLOBAL : KF_DEN_ROWS_LDS;
 }
 
 extern "C" int kf_den_graph_initial_probs(const KfDenGraph *g, float *out) {
@@ -334,12 +385,25 @@ extern "C" KfChain *kf_chain_create(const KfDenGraph *den, int max_seqs, int max
     c->den = den;
     c->max_seqs = max_seqs;
     c->max_frames = max_frames;
-    const int S = den->t->dev.S;
-    const size_t rs = (size_t)den->t->dev.f.nsl * 64;  // slice-ordered state rows
-    bool ok = hipMalloc(&c->alpha_store, (size_t)max_seqs * (max_frames + 1) * rs * 4) == hipSuccess;
-    ok = ok && hipMalloc(&c->beta_store, (size_t)max_seqs * (max_frames + 1) * rs * 4) == hipSuccess;
-    ok = ok && hipMalloc(&c->asum_store, (size_t)max_seqs * (max_frames + 1) * 4) == hipSuccess;
-    ok = ok && hipMalloc(&c->bsum_store, (size_t)max_seqs * (max_frames + 1) * 4) == hipSuccess;
+    bool ok = true;
+    if (den->gt) {  // global rows: one workspace sized from (S, P, max_seqs, max_frames)
+        const size_t bytes = dg_work_bytes(den->gt->dev, max_seqs, max_frames, nullptr, nullptr);
+        if (hipMalloc(&c->dg_ws, bytes) != hipSuccess) {
+            c->dg_ws = nullptr;
+            delete c;
+            kf_take_pending("kf_chain_create workspace");
+            kfc_set_error("kf_chain_create: hipMalloc of the %zu-byte global-rows workspace failed (%d states, %d pdfs, "
+                          "%d sequences, %d frames)", bytes, den->S, den->P, max_seqs, max_frames);
+            return nullptr;
+        }
+        dg_work_bytes(den->gt->dev, max_seqs, max_frames, c->dg_ws, &c->dg_work);
+    } else {
+        const size_t rs = (size_t)den->t->dev.f.nsl * 64;  // slice-ordered state rows
+        ok = hipMalloc(&c->alpha_store, (size_t)max_seqs * (max_frames + 1) * rs * 4) == hipSuccess;
+        ok = ok && hipMalloc(&c->beta_store, (size_t)max_seqs * (max_frames + 1) * rs * 4) == hipSuccess;
+        ok = ok && hipMalloc(&c->asum_store, (size_t)max_seqs * (max_frames + 1) * 4) == hipSuccess;
+        ok = ok && hipMalloc(&c->bsum_store, (size_t)max_seqs * (max_frames + 1) * 4) == hipSuccess;
+    }
     ok = ok && hipMalloc(&c->stats, (size_t)max_seqs * 8 * 4) == hipSuccess;
     // descriptors, row offsets and frame counts in one allocation, laid out as the pinned
     // staging slot, so a layout change is one copy; the sequence and frame weights of a
@@ -383,7 +447,7 @@ static bool compute_args_ok(const KfChain *c, const KfNumBatch *num, const KfCha
         kfc_set_error("kf_chain_compute: NULL argument");
         return false;
     }
-    const int P = c->den->t->dev.P;
+    const int P = c->den->P;
     if (nseq <= 0 || nseq > c->max_seqs || nseq != (int)num->nd->desc.size() || stride <= 0 ||
         ld < P || ldg < P) {
         kfc_set_error("kf_chain_compute: nseq %d (max %d, batch %zu), stride %d, ld %lld/%lld vs P %d",
@@ -529,7 +593,7 @@ static void launch_numerator(KfChain *c, const void *nnet_output, long long ld, 
         hipStream_t saved = kf_stream();
         kf_set_stream((void *)c->side);
         int pn = kf_prof_start(KF_PROF_CHAIN_NUM, num_arcs);
-        launch_num_batch(c->d_desc, (const h16 *)nnet_output, ld, c->den->t->dev.P, nseq, maxT, c->num_lds,
+        launch_num_batch(c->d_desc, (const h16 *)nnet_output, ld, c->den->P, nseq, maxT, c->num_lds,
                          c->side);
         kf_prof_stop(pn);
         kf_set_stream((void *)saved);
@@ -537,11 +601,57 @@ static void launch_numerator(KfChain *c, const void *nnet_output, long long ld, 
     hipEventRecord(c->ev_num, c->side);
 }
 
+// A global-rows graph (chain_den_global.hip): staging, 2 T - 1 recursion launches and the sums,
+// then (once the numerator is in) the posteriors, the assembly and the statistics
+static void launch_denominator_global(KfChain *c, const KfChainOpts *opts, const void *nnet_output, long long ld,
+                                      int nseq, const int32_t *seq_frames, int stride, void *out_grad,
+                                      long long ldg, hipStream_t st) {
+    const DgDev &dd = c->den->gt->dev;
+    double frames = 0;
+    DgRun r{};
+    for (int i = 0; i < nseq; ++i) {
+        frames += seq_frames[i];
+        r.Tm = std::max(r.Tm, (int)seq_frames[i]);
+    }
+    r.nnet = nnet_output;
+    r.ld = ld;
+    r.row0 = c->d_row0;
+    r.frames = c->d_frames;
+    r.stride = stride;
+    r.max_frames = c->max_frames;
+    r.nseq = nseq;
+    r.NQ = dg_pick_nq(nseq);
+    r.ngrp = (nseq + r.NQ - 1) / r.NQ;
+    r.leaky = opts->leaky_hmm_coefficient;
+    r.w = c->dg_work;
+    r.den_out = c->den_out;
+    r.stats = c->stats;
+    r.nums = c->d_desc;
+    r.out_grad = (h16 *)out_grad;
+    r.ldg = ldg;
+    r.opts = *opts;
+    r.seq_w = c->use_seq_w ? c->d_seq_w : nullptr;
+    r.frame_w = c->use_frame_w ? c->d_frame_w : nullptr;
+    r.grad_scale = c->grad_scale;
+    // algorithmic bytes per frame and sequence group: three passes over the records (12, 8 and
+    // 12 B each), the state rows written once and gathered per record, the output row in and out
+    const double bytes = frames / r.NQ * 32.0 * dd.A + frames * (16.0 * dd.S + 6.0 * dd.P);
+    int pd = kf_prof_start(KF_PROF_CHAIN_DEN, bytes);
+    launch_dg_recursions(dd, r);
+    hipStreamWaitEvent(st, c->ev_num, 0);  // the numerator is needed from here on
+    launch_dg_post(dd, r);
+    kf_prof_stop(pd);
+}
+
 // both den recursions in one launch, then (once the numerator is in) the posteriors and
 // the objective assembly; false with the error set
 static bool launch_denominator(KfChain *c, const KfChainOpts *opts, const void *nnet_output, long long ld,
                                int nseq, const int32_t *seq_frames, int stride, void *out_grad,
                                long long ldg, hipStream_t st) {
+    if (c->den->gt) {
+        launch_denominator_global(c, opts, nnet_output, ld, nseq, seq_frames, stride, out_grad, ldg, st);
+        return true;
+    }
     double frames = 0;
     for (int i = 0; i < nseq; ++i) frames += seq_frames[i];
     DenRun r{};
@@ -645,7 +755,7 @@ extern "C" int kf_chain_xent(KfChain *c, const KfNumBatch *num, const KfChainOpt
         kfc_set_error("kf_chain_xent: the numerator batch is not the one of the last kf_chain_compute");
         return -1;
     }
-    const int P = c->den->t->dev.P, nseq = c->last.nseq;
+    const int P = c->den->P, nseq = c->last.nseq;
     if (ldx < P || ldg < P) {
         kfc_set_error("kf_chain_xent: ldx %lld / ldg %lld below P %d", ldx, ldg, P);
         return -1;
@@ -769,6 +879,11 @@ extern "C" void kf_chain_debug_exchange_sys(KfChain *c, int force) {
 // kf_chain_debug_exchange_sys forced agent scope (*forced = 1). 0, or -1 on error.
 extern "C" int kf_chain_debug_census(KfChain *c, int *units, int *local_fwd, int *local_bwd, int *forced, int *G) {
     if (!c) return -1;
+    if (c->den->gt) {  // no exchange on a global-rows graph: zeros
+        for (int *o : {units, local_fwd, local_bwd, forced, G})
+            if (o) *o = 0;
+        return 0;
+    }
     hipStream_t st = kf_stream();
     const int f = c->xbuf.census_local(st), b = c->xbuf2.census_local(st);
     if (f < 0 || b < 0) {

@@ -218,6 +218,67 @@ std::vector<SellRec> sell_scaled(const Sell &h, uint32_t ns) {
     return a;
 }
 
+// ===========================================================================
+// Row tables of the global-rows denominator (chain_den_global.hip)
+// ===========================================================================
+static DgTable build_rows(int nrows, int A, const int32_t *key, const int32_t *f1, const int32_t *f2,
+                          const float *tp, const int32_t *src) {
+    DgTable t;
+    std::vector<int> deg;
+    const std::vector<int> order = sell_order(nrows, A, key, deg);
+    const int padded = (nrows + 63) / 64 * 64;
+    t.perm.assign(padded, -1);
+    t.rowptr.assign(padded + 1, 0);
+    std::vector<int> pos(nrows);
+    for (int r = 0; r < nrows; ++r) {
+        t.perm[r] = order[r];
+        pos[order[r]] = r;
+        t.rowptr[r + 1] = t.rowptr[r] + deg[order[r]];
+    }
+    for (int r = nrows; r < padded; ++r) t.rowptr[r + 1] = t.rowptr[r];
+    t.rec.resize(A);
+    t.isrc.resize(A);
+    std::vector<int> fill(t.rowptr.begin(), t.rowptr.begin() + nrows);
+    for (int a = 0; a < A; ++a) {  // arc order inside every row
+        const int k = fill[pos[key[a]]]++;
+        uint32_t tpu;
+        memcpy(&tpu, &tp[a], 4);
+        t.rec[k] = SellRec{(uint32_t)f1[a] | ((uint32_t)f2[a] << 16), tpu};
+        t.isrc[k] = src[a];
+    }
+    return t;
+}
+
+bool den_global_tables(int S, int P, int A, const int32_t *src, const int32_t *dst, const int32_t *pdf0,
+                       const float *tp, DgHost &out, const char **why) {
+    if (S <= 0 || P <= 0 || A <= 0) {
+        *why = "empty denominator graph";
+        return false;
+    }
+    if (S > 65535 || P > 65535) {
+        *why = "den graph needs num_states, num_pdfs <= 65535 (16-bit arc fields)";
+        return false;
+    }
+    for (int a = 0; a < A; ++a)
+        if (src[a] < 0 || src[a] >= S || dst[a] < 0 || dst[a] >= S || pdf0[a] < 0 ||
+            pdf0[a] >= P || !(tp[a] >= 0.0f)) {
+            *why = "den transition out of range (state, pdf or negative probability)";
+            return false;
+        }
+    // alpha rows live in the f table's row order, beta rows in the b table's: a kernel writes row
+    // r of its own table at position r, and the records name their operands by position
+    const std::vector<int> posf = sell_positions(S, A, dst), posb = sell_positions(S, A, src);
+    std::vector<int32_t> src_f(A), dst_b(A);
+    for (int a = 0; a < A; ++a) {
+        src_f[a] = posf[src[a]];
+        dst_b[a] = posb[dst[a]];
+    }
+    out.f = build_rows(S, A, dst, src_f.data(), pdf0, tp, src);
+    out.b = build_rows(S, A, src, dst_b.data(), pdf0, tp, src);
+    out.q = build_rows(P, A, pdf0, src_f.data(), dst_b.data(), tp, src);
+    return true;
+}
+
 // denominator.go:131-171
 void compute_initial_probs(int S, int A, const int32_t *src, const int32_t *dst, const float *tp,
                    int start, float *out) {

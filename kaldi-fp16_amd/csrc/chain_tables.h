@@ -62,6 +62,24 @@ bool den_host_tables(int S, int P, int A, const int32_t *src, const int32_t *dst
 // records with LDS byte offsets for rows interleaving ns sequences or frames
 std::vector<SellRec> sell_scaled(const Sell &h, uint32_t ns);
 
+// ---- the global-rows denominator (chain_den_global.hip): no size limit but the 16-bit fields ----
+// One table: rows by non-increasing degree (sell_order), padded with empty rows to a multiple of
+// 64, each row's records contiguous and in arc order: rec[rowptr[r] .. rowptr[r + 1]). The records
+// are {f1 | f2 << 16, tp} like the SELL tables', with f1 / f2 plain indices (a row position of the
+// f or b table, or a pdf). isrc: the source STATE of every record (its initial probability weighs
+// the leaky term of alpha'); perm: row -> state or pdf, -1 for padding rows.
+struct DgTable {
+    std::vector<int> perm, rowptr, isrc;
+    std::vector<SellRec> rec;
+};
+struct DgHost {
+    DgTable f, b, q;  // rows = destination states {src, pdf}, source states {dst, pdf}, pdfs {src, dst}
+};
+// validates the graph (1 <= S, P <= 65535, A >= 1, every arc in range) and builds its tables;
+// false with *why set
+bool den_global_tables(int S, int P, int A, const int32_t *src, const int32_t *dst, const int32_t *pdf0,
+                       const float *tp, DgHost &out, const char **why);
+
 // ---- numerator FST host preparation (reverse CSR + pdf groups) -------------
 struct NumHost {  // one FST, local indices
     int S, A, nfinal, start;

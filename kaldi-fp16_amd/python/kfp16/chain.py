@@ -59,6 +59,8 @@ def _sig(name, res, *args):
 for _n in ("kf_chain_last_error", "chain_last_error", "den_last_error"):
     _sig(_n, C.c_char_p)
 _sig("kf_den_graph_create", _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp)
+_sig("kf_den_graph_create_rows", _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i)
+_sig("kf_den_graph_rows", _i, _vp)
 _sig("kf_den_graph_initial_probs", _i, _vp, _vp)
 _sig("kf_den_graph_free", None, _vp)
 _sig("kf_num_batch_create", _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
@@ -104,19 +106,31 @@ def _a(x, dt):
     return np.ascontiguousarray(x, dtype=dt)
 
 
-class DenGraph:
-    """kf_den_graph_create over a dict from synth.make_den_graph."""
+_DEN_ROWS = ("lds", "global", "auto")   # KF_DEN_ROWS_LDS, _GLOBAL, _AUTO
 
-    def __init__(self, g: dict, initial_probs=None):
+
+class DenGraph:
+    """kf_den_graph_create over a dict from synth.make_den_graph. rows: where the denominator
+    keeps its state rows: "lds" (the LDS-resident kernels: at most 4096 pdfs, fewer
+    than 8192 states), "global" (device memory, one launch per frame: up to 65535 of each) or
+    "auto" (lds where the graph fits, global otherwise); .rows is what was chosen."""
+
+    def __init__(self, g: dict, initial_probs=None, rows: str = "lds"):
+        if rows not in _DEN_ROWS:
+            raise ValueError(f"rows {rows!r}: one of {_DEN_ROWS}")
         self.S, self.P, self.A = int(g["S"]), int(g["P"]), int(g["A"])
         self._keep = [_a(g["src"], np.int32), _a(g["dst"], np.int32), _a(g["pdf0"], np.int32),
                       _a(g["tp"], np.float32)]
         ip = None if initial_probs is None else _a(initial_probs, np.float32)
-        self.h = core.kf_den_graph_create(self.S, self.P, self.A,
-                                          *[k.ctypes.data for k in self._keep], int(g["start"]),
-                                          None if ip is None else ip.ctypes.data)
+        args = (self.S, self.P, self.A, *[k.ctypes.data for k in self._keep], int(g["start"]),
+                None if ip is None else ip.ctypes.data)
+        if rows == "lds":
+            self.h = core.kf_den_graph_create(*args)
+        else:
+            self.h = core.kf_den_graph_create_rows(*args, _DEN_ROWS.index(rows))
         if not self.h:
             _raise("kf_den_graph_create")
+        self.rows = _DEN_ROWS[core.kf_den_graph_rows(self.h)] if rows != "lds" else "lds"
 
     def initial_probs(self) -> np.ndarray:
         out = np.empty(self.S, np.float32)

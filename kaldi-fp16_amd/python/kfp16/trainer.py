@@ -144,6 +144,9 @@ class TrainConfig:
     # made before.
     loss_scale: float = 0.0
     loss_scale_growth_interval: int = 2000
+    # den_rows: chain.DenGraph's rows for the den graph the trainer builds: "lds", "global"
+    # (a tree of more than 4096 pdfs or a graph of 8192 states or more needs it) or "auto".
+    den_rows: str = "lds"
 
     def __post_init__(self):
         if self.self_repair and not self.batchnorm_train:
@@ -226,7 +229,7 @@ class EgsTrainer:
         self.max_frames = max_frames
         self.feat = DeviceBuffer(max_frames * 40 * 2)
         self.grad_out = DeviceBuffer(max_frames * self.P * 2)
-        self.dgraph = _chain.DenGraph(den_graph)
+        self.dgraph = _chain.DenGraph(den_graph, rows=self.cfg.den_rows)
         self.objective = _chain.Chain(self.dgraph, max_seqs=max_egs,
                                       max_frames=max(1, max_frames // self.cfg.subsampling_factor + 1))
         if grad_buffer_ptr is not None:
