@@ -1229,3 +1229,14 @@ _sig(core, "kf_im2col_small", _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _ip, _ip, _v
 _sig(core, "kf_col2im_small", _i, _vp, _i, _i, _i, _i, _i, _i, _ip, _ip, _i, _vp, _ll)
 _sig(core, "kf_rows_gemm", _i, _vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i)
 _sig(core, "kf_rows_wgrad", _i, _vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i)
+# kf_lstm.h (projected LSTM sequence operator; the class is kfp16.lstm.Lstmp)
+_sig(core, "kf_lstmp_last_error", C.c_char_p)
+_sig(core, "kf_lstmp_create", _vp, _i, _i, _i, _i, _i, _i, _i)
+_sig(core, "kf_lstmp_free", None, _vp)
+_sig(core, "kf_lstmp_num_params", _ll, _vp)
+_sig(core, "kf_lstmp_set_params", _i, _vp, _vp)
+_sig(core, "kf_lstmp_get_params", _i, _vp, _vp)
+_sig(core, "kf_lstmp_set_clip", _i, _vp, _f)
+_sig(core, "kf_lstmp_forward", _i, _vp, _vp, _ll, _vp, _i, _vp, _ll)
+_sig(core, "kf_lstmp_backward", _i, _vp, _vp, _ll, _vp, _ll, _vp)
+_sig(core, "kf_lstmp_state", _i, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp))
